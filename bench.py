@@ -8,9 +8,21 @@ sequence), 4 action repeats -> 12 800 env frames per learner step, synthetic
 Precision: the reported `value` is measured at the REFERENCE's precision,
 fp32 (reference experiment.py:153-189, 118, 413-415 all run fp32): exact-fp32
 MFMA conv kernels (v_mfma_f32_16x16x4_f32), fp32 LSTM recurrence, fp32
-V-trace / loss / RMSProp.  The bf16 learner (bf16 conv/GEMM operands, fp32
-accumulation and state) is measured in the same run as a second field
-(`config.bf16`), unless --dtype bf16 makes it the headline.
+V-trace / loss / RMSProp.  --dtype bf16 makes the bf16 learner (bf16
+conv/GEMM operands, fp32 accumulation and state) the headline instead.
+
+A plain run does only what the headline figure needs: set up, warm up, time
+the K steps, write the outputs (--dump-outputs) and print the JSON line.
+--full adds the measurements that take runs of their own: the bf16 learner
+as a second field (`config.bf16`, with --dtype fp32), the standalone H2D
+bandwidth of one batch slab (`config.h2d_slab`) and, with N>1 ranks, the
+standalone all-reduce of the flat gradient buffer
+(`config.dist.allreduce_ms_standalone`).
+
+--dump-outputs DIR writes what the last timed step handed its caller, as
+float32 .npy files: DIR/loss.npy (the step's loss) and DIR/params.npy (the
+flat parameter buffer after the step's update).  Batches and initial weights
+are seeded, so two runs with the same arguments see identical inputs.
 
 One process per GPU; N>1 is weak scaling (each learner consumes its own B=32
 batch, gradients summed with one RCCL all-reduce).  Every timed step does the
@@ -20,6 +32,7 @@ re-unroll, V-trace, loss, backward, gradient all-reduce, RMSProp with
 on-device LR decay, frame-counter increment.
 
 Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--dtype fp32|bf16]
+                       [--full] [--dump-outputs DIR]
 
 Multi-GPU: either launched by torch.distributed.run (one rank per GPU, the
 env carries RANK/WORLD_SIZE/...), or plain `python bench.py --gpus N`: then
@@ -198,9 +211,21 @@ METRIC = ('learner env-frames/sec, IMPALA deep-ResNet+LSTM, batch=32 '
 BASELINE_FPS = 250000.0  # BASELINE.md §B best published single-learner figure
 
 
-def measure(args, dtype, device, backend, rank, world):
+def dump_outputs(out_dir, loss, learner):
+  """The last timed step's results as float32 .npy files: its loss and the
+  flat parameter buffer its update left."""
+  import numpy as np
+  os.makedirs(out_dir, exist_ok=True)
+  arrays = {'loss': loss.detach().reshape(1), 'params': learner.flat.params}
+  for name, t in arrays.items():
+    np.save(os.path.join(out_dir, name + '.npy'),
+            t.detach().to(torch.float32).cpu().numpy())
+
+
+def measure(args, dtype, device, backend, rank, world, dump_dir=None):
   """Builds one learner at `dtype` and times K steps after W warmups.
-  Returns a dict of per-rank results (dt is the MAX over ranks)."""
+  Returns a dict of per-rank results (dt is the MAX over ranks).  dump_dir:
+  rank 0 writes the last step's outputs there (dump_outputs)."""
   flags = flags_lib.default_flags(
       batch_size=args.batch_size, unroll_length=args.unroll_length,
       torso=args.torso, dtype=dtype, height=args.height, width=args.width,
@@ -264,17 +289,22 @@ def measure(args, dtype, device, backend, rank, world):
     for e in slot_ready + slot_free:
       e.record()
     comp = torch.cuda.current_stream(device)
-    # standalone H2D bandwidth of one batch slab on the copy stream (reported:
-    # the per-step prefetch hides behind compute only while it is shorter)
-    h2d_ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
-    torch.cuda.synchronize(device)
-    with torch.cuda.stream(copy_stream):
-      h2d_ev[0].record(copy_stream)
-      dev_flat[1].copy_from(host_flat[1])
-      h2d_ev[1].record(copy_stream)
-    torch.cuda.synchronize(device)
-    h2d_ms = h2d_ev[0].elapsed_time(h2d_ev[1])
-    h2d_mb = dev_flat[1].nbytes / 1e6
+    h2d_slab = None
+    if args.full:
+      # standalone H2D bandwidth of one batch slab on the copy stream
+      # (reported: the per-step prefetch hides behind compute only while it
+      # is shorter)
+      h2d_ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+      torch.cuda.synchronize(device)
+      with torch.cuda.stream(copy_stream):
+        h2d_ev[0].record(copy_stream)
+        dev_flat[1].copy_from(host_flat[1])
+        h2d_ev[1].record(copy_stream)
+      torch.cuda.synchronize(device)
+      h2d_ms = h2d_ev[0].elapsed_time(h2d_ev[1])
+      h2d_mb = dev_flat[1].nbytes / 1e6
+      h2d_slab = {'mbytes': round(h2d_mb, 1), 'ms': round(h2d_ms, 3),
+                  'gbps': round(h2d_mb / max(h2d_ms, 1e-6), 1)}
   # diagnostic only (never the reported benchmark): SA_BENCH_SKIP_H2D=1 drops
   # the per-step host->device prefetch of the next batch
   skip_h2d = measure_env('SA_BENCH_SKIP_H2D') == '1'
@@ -337,8 +367,9 @@ def measure(args, dtype, device, backend, rank, world):
   if world > 1:
     # per-rank step time (the reported dt is the max), the all-reduce window
     # of the last step (begin of the early bucket -> end of the last one, so
-    # it spans the overlapped torso backward) and a standalone all-reduce of
-    # the whole flat gradient buffer (the bare collective's cost)
+    # it spans the overlapped torso backward) and, with --full, a standalone
+    # all-reduce of the whole flat gradient buffer (the bare collective's
+    # cost)
     per = [torch.zeros(1, dtype=torch.float64, device=device)
            for _ in range(world)]
     torch.distributed.all_gather(
@@ -349,6 +380,7 @@ def measure(args, dtype, device, backend, rank, world):
     if learner.grad_sync is not None:
       dist_extra['allreduce_window_ms'] = round(
           1000 * learner.grad_sync.last_time_s, 3)
+    if learner.grad_sync is not None and args.full:
       g = learner.flat.grads
       reps = 10
       sync()
@@ -359,14 +391,15 @@ def measure(args, dtype, device, backend, rank, world):
       dist_extra['allreduce_ms_standalone'] = round(
           1000 * (time.perf_counter() - t1) / reps, 3)
       dist_extra['allreduce_mbytes'] = round(g.numel() * 4 / 1e6, 2)
+  if dump_dir and rank == 0:
+    dump_outputs(dump_dir, loss, learner)
   res = {
       'dt': dt, 'loss_finite': bool(torch.isfinite(loss).item()),
       'enqueue_s': t_enq, 'frames_per_step': learner.frames_per_step,
       'health': learner.health(), 'torso': torso_precision(agent),
       'hip_graph': use_graph, 'h2d_prefetch': not skip_h2d,
       'h2d_prefetch_sync': 'host' if host_sync else 'device',
-      'h2d_slab': ({'mbytes': round(h2d_mb, 1), 'ms': round(h2d_ms, 3),
-                    'gbps': round(h2d_mb / max(h2d_ms, 1e-6), 1)} if cuda else None),
+      'h2d_slab': h2d_slab if cuda else None,
       'dist_extra': dist_extra,
   }
   del learner, agent, graphs
@@ -391,8 +424,16 @@ def main():
   ap.add_argument('--backend', default='auto', choices=['auto', 'torch', 'hip'])
   ap.add_argument('--dtype', default='fp32', choices=['fp32', 'bf16'],
                   help='precision of the reported value (fp32 = reference)')
+  ap.add_argument('--full', action='store_true',
+                  help='also run the measurements beside the headline: the '
+                       'bf16 learner (config.bf16), the standalone H2D slab '
+                       'copy, the standalone all-reduce (N>1)')
+  ap.add_argument('--dump-outputs', dest='dump_outputs', default=None,
+                  metavar='DIR',
+                  help='write the last timed step\'s outputs (loss, updated '
+                       'flat parameters) as DIR/<name>.npy, float32')
   ap.add_argument('--also_bf16', type=int, default=1,
-                  help='with --dtype fp32: also time the bf16 learner')
+                  help='with --full --dtype fp32: also time the bf16 learner')
   ap.add_argument('--instructions', type=int, default=0,
                  help='1: DMLab-style batches with instruction strings '
                       '(language LSTM in the core input).')
@@ -455,9 +496,11 @@ def main():
       ops.load()  # a GPU run without the kernels fails loudly (no silent torch)
       backend = 'hip'
 
-  main_res = measure(args, args.dtype, device, backend, rank, world)
+  main_res = measure(args, args.dtype, device, backend, rank, world,
+                     dump_dir=args.dump_outputs)
   extra = None
-  if (args.dtype == 'fp32' and args.also_bf16 and backend == 'hip' and
+  if (args.full and args.dtype == 'fp32' and args.also_bf16 and
+      backend == 'hip' and
       args.torso == 'deep'):  # the shallow torso has fp32 kernels only
     extra = measure(args, 'bf16', device, backend, rank, world)
 

@@ -3,8 +3,9 @@ container round trip, UDMF write/parse, map soundness, one WAD per scenario
 the table names, and the simulator backend running on them.
 
 Parity with the reference's own WADs is not the claim (they are binary
-assets with compiled ACS); the reference UDMF maps are only used, read-only,
-to check that the parser reads real ZDoom TEXTMAPs."""
+assets with compiled ACS); the TEXTMAP lumps of the reference's UDMF maps
+(map geometry and things only, no scripts) are kept as WADs under
+tests/golden/doom_udmf/ to check that the parser reads real ZDoom TEXTMAPs."""
 import glob
 import os
 
@@ -14,7 +15,8 @@ import pytest
 from scalable_agent_amd.envs.doom import scenario_maps, scenarios
 from scalable_agent_amd.envs.doom import wad as W
 
-REF_SCEN = '/root/reference/envs/doom/scenarios'
+REF_SCEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden',
+                        'doom_udmf')
 
 
 def test_wad_container_roundtrip(tmp_path):
@@ -92,7 +94,6 @@ def test_every_scenario_wad_is_built_and_sound(tmp_path):
       assert fa.read() == fb.read()
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_SCEN), reason='reference not present')
 def test_parser_reads_reference_udmf_maps():
   n = 0
   for p in sorted(glob.glob(os.path.join(REF_SCEN, '*.wad'))):
@@ -104,7 +105,7 @@ def test_parser_reads_reference_udmf_maps():
       m = W.parse_udmf(ml['TEXTMAP'].decode('latin1'))
       assert m['namespace'] == 'zdoom' and m['vertices'] and m['things']
       n += 1
-  assert n >= 5
+  assert n == 7  # six WADs, cig.wad holds two maps
 
 
 def test_wad_path_falls_back_to_generated(monkeypatch, tmp_path):

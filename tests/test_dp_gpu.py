@@ -103,7 +103,7 @@ def test_bench_two_ranks_one_card(cuda):
          '--nproc-per-node', '2', '--master-addr', '127.0.0.1',
          '--master-port', str(port), os.path.join(root, 'bench.py'),
          '--gpus', '2', '--steps', '3', '--warmup', '2', '--batch_size', '4',
-         '--unroll_length', '10']
+         '--unroll_length', '10', '--full']  # --full: the bf16 learner too
   env = dict(os.environ, PYTHONPATH=root, SA_DIST_BACKEND='gloo',
              OMP_NUM_THREADS='2')
   r = subprocess.run(cmd, capture_output=True, text=True, timeout=240, env=env)
