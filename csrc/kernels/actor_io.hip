@@ -13,23 +13,12 @@
 // With offset_ptr the offset is read from device memory, so a captured
 // inference graph draws fresh samples on every replay (the graph bumps it).
 #include "launchers.h"
+#include "philox.h"
 
 namespace sa {
 namespace {
 
 constexpr int kMaxA = 32;
-
-__device__ __forceinline__ uint4 philox4x32_10(uint4 c, uint2 k) {
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    const unsigned lo0 = 0xD2511F53u * c.x, hi0 = __umulhi(0xD2511F53u, c.x);
-    const unsigned lo1 = 0xCD9E8D57u * c.z, hi1 = __umulhi(0xCD9E8D57u, c.z);
-    c = make_uint4(hi1 ^ c.y ^ k.x, lo1, hi0 ^ c.w ^ k.y, lo0);
-    k.x += 0x9E3779B9u;
-    k.y += 0xBB67AE85u;
-  }
-  return c;
-}
 
 // heads + Gumbel-max sample of one row (one wave)
 __device__ __forceinline__ void sample_row(

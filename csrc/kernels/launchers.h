@@ -198,6 +198,47 @@ void actor_head_sample_launch(const float* h, const float* wp, const float* bp,
                               unsigned long long* offset_ptr, int advance,
                               hipStream_t stream);
 
+// ---- actor_core.hip --------------------------------------------------------
+// The actor's T = 1 core step in one launch (exact fp32): x-projection +
+// LSTM-256 step + heads + Gumbel-max sample (+ the board epilogue when `out`
+// is set).  K % 16 == 0, K <= min(kmax, actor_core_max_k()), A <= 32.
+struct ActorCoreStep {
+  const float* h_aug;   // [R, ld]: [relu(fc), clip(r), one_hot(a), instr|0]
+  const uint8_t* done;  // [R]
+  const float* c_in;    // [R, 256]
+  const float* h_in;    // [R, 256] (never h2)
+  const float* wpk;     // actor_core_pack_launch's output for kmax
+  const float* b_lstm;  // [1024]
+  const float* wp;      // [256, A]
+  const float* bp;      // [A]
+  const float* wb;      // [256, Kv], value head 0 is read
+  const float* bb;      // [Kv]
+  float* c2;            // outputs
+  float* h2;
+  float* logits;
+  float* baseline;
+  int64_t* action;
+  unsigned* tickets;            // >= ceil(R / 16) words, zero between launches
+  unsigned long long* counter;  // nullptr (use `offset`) or {offset, waves done}
+  unsigned long long seed, offset;
+  int R, ld, K, kmax, A, Kv;
+  // board epilogue: out == nullptr for none.  c / h [R, 256] take c2 / h2
+  // where mask > 0 (they may be c_in / h_in); action, logits, baseline, c2,
+  // h2 are packed at dword offsets off_dw[] of slot r / M (16-byte aligned
+  // c / h fields); masked_only as in board_epilogue_launch
+  const float* mask;
+  float* c;
+  float* h;
+  void* out;
+  int off_dw[5];
+  int M, slot_dw, masked_only;
+};
+int actor_core_max_k();
+void actor_core_step_launch(const ActorCoreStep& p, hipStream_t stream);
+// lstm_kernel [f_in + 256, 1024] -> wpk [(kmax + 256) * 1024] (kmax >= f_in)
+void actor_core_pack_launch(const float* w, float* wpk, int f_in, int kmax,
+                            hipStream_t stream);
+
 // ---- calibration ----------------------------------------------------------
 void noop_launch(int blocks, int threads, int* p, hipStream_t s);
 

@@ -283,6 +283,124 @@ void board_epilogue(std::vector<at::Tensor> fields, std::vector<int64_t> offs, a
                             stream());
 }
 
+// lstm_kernel [f_in + 256, 1024] -> wpk, the B operand of actor_core_step:
+// W_x rows padded to kmax = wpk.numel() / 1024 - 256, then W_h.
+void actor_core_pack(at::Tensor kernel, int64_t f_in, at::Tensor wpk) {
+  LB_CHECK(kernel); LB_CHECK(wpk); LB_F32(kernel); LB_F32(wpk);
+  TORCH_CHECK(kernel.dim() == 2 && kernel.size(0) == f_in + 256 && kernel.size(1) == 1024,
+              "kernel must be [f_in + 256, 1024]");
+  const int64_t kmax = wpk.numel() / 1024 - 256;
+  TORCH_CHECK(wpk.numel() == (kmax + 256) * 1024 && kmax >= f_in && kmax % 16 == 0 &&
+                  kmax <= sa::actor_core_max_k(),
+              "wpk must hold (kmax + 256) * 1024 floats, f_in <= kmax % 16 == 0");
+  const c10::DeviceGuard guard(kernel.device());
+  sa::actor_core_pack_launch(kernel.data_ptr<float>(), wpk.data_ptr<float>(),
+                             static_cast<int>(f_in), static_cast<int>(kmax), stream());
+}
+
+// The actor's T = 1 core step in one launch (kernels/actor_core.hip):
+// h_aug [R, K] (K % 16 == 0), done [R], c_in / h_in [R, 256], wpk from
+// actor_core_pack, heads wp [256, A] / bp / wb [256, Kv] / bb [Kv] (value
+// head 0), tickets int32 (zero, >= ceil(R / 16) words), Philox (seed, offset)
+// or counter = the int64 pair {offset, waves done} advanced by the kernel.
+// Board epilogue (all or none of epi_*): c_in / h_in take c2 / h2 where
+// epi_mask > 0 and {action, logits, baseline, c2, h2} are packed into epi_out
+// (or the device-accessible address epi_out_addr: masked rows only) as
+// board_epilogue does.  -> {action, logits, baseline, c2, h2}
+std::vector<at::Tensor> actor_core_step(
+    at::Tensor h_aug, at::Tensor done, at::Tensor c_in, at::Tensor h_in, at::Tensor wpk,
+    at::Tensor b_lstm, at::Tensor wp, at::Tensor bp, at::Tensor wb, at::Tensor bb,
+    at::Tensor tickets, int64_t seed, int64_t offset, c10::optional<at::Tensor> counter,
+    c10::optional<at::Tensor> epi_mask, std::vector<int64_t> epi_offs,
+    c10::optional<at::Tensor> epi_out, int64_t epi_M, int64_t epi_slot_bytes,
+    int64_t epi_out_addr) {
+  LB_CHECK(h_aug); LB_CHECK(done); LB_CHECK(c_in); LB_CHECK(h_in); LB_CHECK(wpk);
+  LB_CHECK(b_lstm); LB_CHECK(wp); LB_CHECK(bp); LB_CHECK(wb); LB_CHECK(bb); LB_CHECK(tickets);
+  LB_F32(h_aug); LB_F32(c_in); LB_F32(h_in); LB_F32(wpk); LB_F32(b_lstm);
+  LB_F32(wp); LB_F32(bp); LB_F32(wb); LB_F32(bb);
+  TORCH_CHECK(h_aug.dim() == 2, "h_aug must be [R, K]");
+  const int64_t R = h_aug.size(0), K = h_aug.size(1);
+  const int64_t kmax = wpk.numel() / 1024 - 256;
+  TORCH_CHECK(wpk.numel() == (kmax + 256) * 1024 && K % 16 == 0 && K >= 16 && K <= kmax &&
+                  kmax <= sa::actor_core_max_k(), "h_aug width / packed weights mismatch");
+  TORCH_CHECK(done.numel() == R && c_in.dim() == 2 && c_in.size(0) == R && c_in.size(1) == 256 &&
+                  c_in.sizes() == h_in.sizes() && b_lstm.numel() == 1024, "core shapes");
+  TORCH_CHECK(wp.dim() == 2 && wp.size(0) == 256 && wb.dim() == 2 && wb.size(0) == 256,
+              "heads must be [256, A] / [256, Kv]");
+  const int64_t A = wp.size(1), Kv = wb.size(1);
+  TORCH_CHECK(A >= 1 && A <= sa::actor_head_max_actions(), "1 <= num_actions <= 32");
+  TORCH_CHECK(bp.numel() == A && Kv >= 1 && bb.numel() == Kv, "head biases");
+  TORCH_CHECK(257 + A <= K, "h_aug narrower than [h, r, one_hot(a)]");
+  TORCH_CHECK(tickets.scalar_type() == at::kInt && tickets.numel() >= (R + 15) / 16,
+              "tickets must be int32 with one word per 16 rows");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(c_in.data_ptr()) % 16 == 0 &&
+                  reinterpret_cast<uintptr_t>(h_in.data_ptr()) % 16 == 0,
+              "c / h must be 16-byte aligned");
+  sa::ActorCoreStep p{};
+  if (counter.has_value()) {
+    LB_CHECK(*counter);
+    TORCH_CHECK(counter->scalar_type() == at::kLong && counter->numel() == 2,
+                "counter must be the int64 pair {offset, waves done}");
+    p.counter = reinterpret_cast<unsigned long long*>(counter->data_ptr());
+  }
+  const c10::DeviceGuard guard(h_aug.device());
+  auto action = at::empty({R}, h_aug.options().dtype(at::kLong));
+  auto logits = at::empty({R, A}, h_aug.options());
+  auto baseline = at::empty({R}, h_aug.options());
+  auto c2 = at::empty({R, 256}, h_aug.options());
+  auto h2 = at::empty({R, 256}, h_aug.options());
+  if (epi_mask.has_value()) {
+    LB_CHECK(*epi_mask); LB_F32(*epi_mask);
+    TORCH_CHECK(epi_out.has_value(), "epilogue needs the output block");
+    LB_CHECK(*epi_out);
+    TORCH_CHECK(epi_out->scalar_type() == at::kByte, "epi_out must be uint8");
+    TORCH_CHECK(epi_mask->numel() == R && epi_offs.size() == 5, "mask [R], five field offsets");
+    TORCH_CHECK(epi_M >= 1 && R % epi_M == 0 && epi_slot_bytes % 16 == 0 &&
+                    epi_out->numel() >= (R / epi_M) * epi_slot_bytes, "board geometry");
+    const int64_t per[5] = {8, 4 * A, 4, 1024, 1024};  // bytes per row
+    for (int f = 0; f < 5; ++f) {
+      TORCH_CHECK(epi_offs[f] >= 0 && epi_offs[f] % (f >= 3 ? 16 : 4) == 0 &&
+                      epi_offs[f] + epi_M * per[f] <= epi_slot_bytes,
+                  "field offsets must lie inside the slot block (c / h 16-byte aligned)");
+      p.off_dw[f] = static_cast<int>(epi_offs[f] / 4);
+    }
+    p.out = epi_out_addr ? reinterpret_cast<void*>(epi_out_addr) : epi_out->data_ptr();
+    TORCH_CHECK(reinterpret_cast<uintptr_t>(p.out) % 16 == 0, "out 16-byte aligned");
+    p.mask = epi_mask->data_ptr<float>();
+    p.c = c_in.data_ptr<float>();
+    p.h = h_in.data_ptr<float>();
+    p.M = static_cast<int>(epi_M);
+    p.slot_dw = static_cast<int>(epi_slot_bytes / 4);
+    p.masked_only = epi_out_addr != 0;
+  }
+  p.h_aug = h_aug.data_ptr<float>();
+  p.done = mask_ptr(done);
+  p.c_in = c_in.data_ptr<float>();
+  p.h_in = h_in.data_ptr<float>();
+  p.wpk = wpk.data_ptr<float>();
+  p.b_lstm = b_lstm.data_ptr<float>();
+  p.wp = wp.data_ptr<float>();
+  p.bp = bp.data_ptr<float>();
+  p.wb = wb.data_ptr<float>();
+  p.bb = bb.data_ptr<float>();
+  p.c2 = c2.data_ptr<float>();
+  p.h2 = h2.data_ptr<float>();
+  p.logits = logits.data_ptr<float>();
+  p.baseline = baseline.data_ptr<float>();
+  p.action = action.data_ptr<int64_t>();
+  p.tickets = reinterpret_cast<unsigned*>(tickets.data_ptr<int>());
+  p.seed = static_cast<unsigned long long>(seed);
+  p.offset = static_cast<unsigned long long>(offset);
+  p.R = static_cast<int>(R);
+  p.ld = static_cast<int>(K);
+  p.K = static_cast<int>(K);
+  p.kmax = static_cast<int>(kmax);
+  p.A = static_cast<int>(A);
+  p.Kv = static_cast<int>(Kv);
+  sa::actor_core_step_launch(p, stream());
+  return {action, logits, baseline, c2, h2};
+}
+
 // C[:, :N] (+)= op(A) op(B) with the fused epilogue of kernels/gemm_f32.h.
 // A / B / C / mask may be row slices of wider row-major matrices (row stride
 // = stride(0), unit column stride).  op(A) = A^T when ta (A is [K, M]),
@@ -533,4 +651,15 @@ void register_learner_ops(pybind11::module& m) {
         pybind11::arg("wp"), pybind11::arg("bp"), pybind11::arg("wb"),
         pybind11::arg("bb"), pybind11::arg("seed"), pybind11::arg("offset"),
         pybind11::arg("offset_dev") = pybind11::none());
+  m.def("actor_core_pack", &actor_core_pack, pybind11::arg("kernel"), pybind11::arg("f_in"),
+        pybind11::arg("wpk"));
+  m.def("actor_core_step", &actor_core_step, pybind11::arg("h_aug"), pybind11::arg("done"),
+        pybind11::arg("c_in"), pybind11::arg("h_in"), pybind11::arg("wpk"),
+        pybind11::arg("b_lstm"), pybind11::arg("wp"), pybind11::arg("bp"), pybind11::arg("wb"),
+        pybind11::arg("bb"), pybind11::arg("tickets"), pybind11::arg("seed"),
+        pybind11::arg("offset"), pybind11::arg("counter") = pybind11::none(),
+        pybind11::arg("epi_mask") = pybind11::none(),
+        pybind11::arg("epi_offs") = std::vector<int64_t>(),
+        pybind11::arg("epi_out") = pybind11::none(), pybind11::arg("epi_M") = 1,
+        pybind11::arg("epi_slot_bytes") = 0, pybind11::arg("epi_out_addr") = 0);
 }

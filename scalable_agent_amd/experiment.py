@@ -152,7 +152,19 @@ def _make_agent(flags, num_actions, frame_shape, device, seed, dtype=None):
   return Agent(num_actions, torso=flags.torso, frame_shape=frame_shape,
                seed=seed, backend=backend, compute_dtype=cdt,
                num_value_heads=num_value_heads(flags),
-               pipeline_chunks=getattr(flags, 'pipeline_chunks', 1))
+               pipeline_chunks=getattr(flags, 'pipeline_chunks', 1),
+               actor_core=getattr(flags, 'actor_core', 'ops'))
+
+
+def _log_actor_core(flags, model):
+  """Which core the inference model's steps run (--actor_core)."""
+  asked = getattr(flags, 'actor_core', 'ops')
+  used = model.actor_core
+  if asked == used:
+    log.info('actor inference core: %s', used)
+  else:
+    log.info('actor inference core: %s (--actor_core=%s needs an fp32 HIP '
+             'agent on a GPU with at most 32 actions)', used, asked)
 
 
 class EpisodeLogger(object):
@@ -587,6 +599,8 @@ def train(flags):
         lane_model = inference_lib.InferenceModel(
             inf_agent, inf_device, use_instr,
             seed=flags.seed + 17 * rank + 7919 * lane)
+        if lane == 0:
+          _log_actor_core(flags, lane_model)
         servers.append(BoardServer(lane_model, lane_board,
                                    gather_us=flags.inference_gather_us,
                                    depth=flags.inference_board_depth))
@@ -608,6 +622,7 @@ def train(flags):
                             flags.seed, dtype=inf_dtype)
     model = inference_lib.InferenceModel(inf_agent, inf_device, use_instr,
                                          seed=flags.seed + 17 * rank)
+    _log_actor_core(flags, model)
     model.publish(learner.flat.params)
     infer = inference_lib.make_batched_infer(
         model, flags.inference_min_batch, flags.inference_max_batch,

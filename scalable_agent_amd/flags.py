@@ -108,6 +108,12 @@ def build_parser() -> argparse.ArgumentParser:
                  help='Actor-inference compute dtype (auto = --dtype); bf16 '
                       'trades behaviour-policy precision (V-trace corrects '
                       'for the policy lag either way) for actor throughput.')
+  p.add_argument('--actor_core', default='ops', choices=['ops', 'fused'],
+                 help='Actor-inference core step of an fp32 HIP agent: ops = '
+                      'x-projection GEMM, LSTM step and heads + sampler '
+                      'kernels; fused = ONE kernel after the torso-FC GEMM '
+                      '(on an inference board it also commits the state and '
+                      'packs the outputs).  bf16 inference runs ops.')
   p.add_argument('--inference_device', default='auto',
                  help='Device of the actor-inference model: auto = the '
                       'learner device; e.g. cuda:1 or cpu.')

@@ -93,17 +93,29 @@ class InferenceModel(object):
     if hasattr(self.agent, 'refresh_inference_cache'):
       self.agent.refresh_inference_cache()
 
+  @property
+  def actor_core(self):
+    """'fused' when this model's steps run the one-kernel actor core
+    (Agent(actor_core='fused') where it applies), else 'ops'."""
+    fused = getattr(self.agent, 'actor_core_fused', None)
+    return ('fused' if fused is not None and
+            fused(self._gen, self.device.type == 'cuda') else 'ops')
+
   @torch.no_grad()
   def step_device(self, last_action, reward, done, frame, instr_ids,
-                  instr_len, c, h, has_instr):
+                  instr_len, c, h, has_instr, epilogue=None):
     """Device tensors in -> device tensors (action, logits, baseline, c, h).
-    Call under `self._lock` on `self.stream`."""
+    Call under `self._lock` on `self.stream`.  epilogue (only when
+    `actor_core == 'fused'`): an ops.actor_core.BoardEpilogue - the step also
+    commits the masked rows of the new state into c / h and packs the
+    outputs into the board's block."""
     instr = (instr_ids, instr_len) if (self.use_instruction and
                                        has_instr) else None
     env_output = StepOutput(reward, StepOutputInfo(None, None), done,
                             (frame, instr))
+    kw = {} if epilogue is None else {'epilogue': epilogue}
     out, (c2, h2) = self.agent.step(last_action, env_output, (c, h),
-                                    generator=self._gen)
+                                    generator=self._gen, **kw)
     return [out.action, out.policy_logits, out.baseline, c2, h2]
 
   @torch.no_grad()

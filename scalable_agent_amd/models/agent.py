@@ -122,8 +122,14 @@ class Agent(nn.Module):
 
   def __init__(self, num_actions, torso='shallow', frame_shape=(72, 96, 3),
                seed=None, backend='torch', compute_dtype=torch.float32,
-               num_value_heads=1, pipeline_chunks=1):
+               num_value_heads=1, pipeline_chunks=1, actor_core='ops'):
     super().__init__()
+    # 'fused': the T = 1 inference step after the torso-FC GEMM is ONE kernel
+    # (ops/actor_core.py) where it applies (actor_core_fused); 'ops': the
+    # x-projection, LSTM step and heads + sampler ops
+    if actor_core not in ('ops', 'fused'):
+      raise ValueError('unknown actor_core %r' % (actor_core,))
+    self.actor_core = actor_core
     # > 1 (HIP backend on a GPU): the learner unroll is split into this many
     # time chunks; chunk k's LSTM recurrence runs on a side stream while the
     # conv torso of chunk k+1 runs on the main stream (see _pipelined_core).
@@ -469,6 +475,16 @@ class Agent(nn.Module):
       cache['w16'] = (
           torch.empty(self.linear_w.shape, dtype=bf, device=dev),
           torch.empty(k_max, self.lstm_kernel.shape[1], dtype=bf, device=dev))
+    if self.actor_core == 'fused':
+      # [W_x[:K_max]; W_h] in the fused core step's B-operand layout
+      from ..ops import actor_core
+      k_max = actor_core.packed_rows(self.num_actions)
+      cache['wpk'] = torch.empty((k_max + CORE_SIZE) * 4 * CORE_SIZE,
+                                 device=dev)
+    if self.num_value_heads > 1:
+      # value head 0 contiguous, for the one-head sampler kernel
+      cache['wb0'] = (torch.empty(CORE_SIZE, 1, device=dev),
+                      torch.empty(1, device=dev))
     self._inference_cache = cache
     self.refresh_inference_cache()
 
@@ -487,6 +503,53 @@ class Agent(nn.Module):
       w16_fc, wx16 = cache['w16']
       w16_fc.copy_(self.linear_w)
       wx16.copy_(self.lstm_kernel[:wx16.shape[0]])
+    if cache.get('wpk') is not None:
+      ops.actor_core.actor_core_pack(self.lstm_kernel, self.num_actions,
+                                     out=cache['wpk'])
+    if cache.get('wb0') is not None:
+      cache['wb0'][0].copy_(self.baseline_w[:, :1])
+      cache['wb0'][1].copy_(self.baseline_b[:1])
+
+  def actor_core_fused(self, generator, cuda=True):
+    """True when `actor_core='fused'` is honoured for a T = 1 no-grad step
+    of CUDA tensors sampled from `generator`: fp32 HIP agent whose fused core
+    applies, at most 32 actions, a PhiloxStream.  Otherwise the ops path
+    runs."""
+    from ..ops.heads import PhiloxStream
+    return (self.actor_core == 'fused' and self.backend == 'hip' and cuda and
+            self.compute_dtype == torch.float32 and self.fused_core_ready() and
+            self.num_actions <= 32 and isinstance(generator, PhiloxStream))
+
+  def _fused_step(self, actions, env_outputs, core_state, generator, epilogue):
+    """The T = 1 actor step with the fused core: torso, the torso-FC GEMM
+    (+ the instruction copy), then ONE kernel for the x-projection, the LSTM
+    step, the heads, the sample and (epilogue) the board's commit + packing."""
+    from .. import ops
+    reward, _, done, (frame, instr) = env_outputs
+    B = actions.shape[1]
+    frames = frame.reshape((B,) + tuple(frame.shape[2:]))
+    feats = self.conv_features(frames)
+    instr_enc = None
+    if instr is not None:
+      instr_enc = self.instruction_encoding(
+          (instr[0].reshape(B, -1), instr[1].reshape(B)), B,
+          frames.device).float().contiguous()
+    h_aug = ops.core.core_input_f32(
+        feats.contiguous(), self.linear_w, self.linear_b,
+        reward.reshape(B).to(torch.float32).contiguous(),
+        actions.reshape(B).to(torch.int64).contiguous(), self.num_actions,
+        instr_enc)
+    cache = self._inference_cache
+    wpk = None if cache is None else cache.get('wpk')
+    if wpk is None:  # no inference cache: packed per call
+      wpk = ops.actor_core.actor_core_pack(self.lstm_kernel, self.num_actions)
+    c, h = core_state
+    action, logits, baseline, c2, h2 = ops.actor_core_step(
+        h_aug, done.reshape(B).to(torch.bool), c, h, wpk, self.lstm_bias,
+        self.policy_w, self.policy_b, self.baseline_w, self.baseline_b,
+        generator, epilogue=epilogue)
+    return AgentOutput(action.view(1, B), logits.view(1, B, -1),
+                       baseline.view(1, B)), (c2, h2)
 
   def fused_core_ready(self, instr=None):
     """True when the HIP learner path (fused torso-FC/core-input/LSTM op,
@@ -529,26 +592,47 @@ class Agent(nn.Module):
 
   def _fused_sampler_ready(self, core_out, task_ids, generator):
     """Heads + Gumbel-max sampling as one HIP kernel (actor_io.hip) when the
-    caller drives a device-side PhiloxStream."""
+    caller drives a device-side PhiloxStream.  A multi-head agent without
+    task ids reports value head 0, as `heads` does."""
     from ..ops.heads import PhiloxStream
     return (isinstance(generator, PhiloxStream) and self.backend == 'hip' and
-            core_out.is_cuda and self.num_value_heads == 1 and
-            task_ids is None and self.num_actions <= 32)
+            core_out.is_cuda and task_ids is None and self.num_actions <= 32)
+
+  def _value_head0(self):
+    """(baseline_w, baseline_b) of value head 0, contiguous [256, 1] / [1]:
+    the cached copy of an inference agent, else sliced per call."""
+    if self.num_value_heads == 1:
+      return self.baseline_w, self.baseline_b
+    cache = self._inference_cache
+    if (cache is not None and cache.get('wb0') is not None and
+        not torch.is_grad_enabled()):
+      return cache['wb0']
+    return self.baseline_w[:, :1].contiguous(), self.baseline_b[:1].contiguous()
 
   def unroll(self, actions, env_outputs, core_state, sample=True,
-             generator=None, task_ids=None):
+             generator=None, task_ids=None, epilogue=None):
     """Unrolls over T steps (experiment.py:219-237).
 
     actions: [T,B] last actions; env_outputs: StepOutput with [T,B,...]
     fields whose observation is (frame uint8 [T,B,H,W,C], instr or None).
+    epilogue: an ops.actor_core.BoardEpilogue folded into the fused core
+    step (callers pass it only when actor_core_fused() holds).
     """
     T, B = actions.shape[0], actions.shape[1]
+    if (sample and T == 1 and task_ids is None and
+        not torch.is_grad_enabled() and
+        self.actor_core_fused(generator, env_outputs[3][0].is_cuda)):
+      return self._fused_step(actions, env_outputs, core_state, generator,
+                              epilogue)
+    if epilogue is not None:
+      raise ValueError('a board epilogue needs the fused actor core')
     core_out, core_state = self.unroll_core(actions, env_outputs, core_state)
     if sample and self._fused_sampler_ready(core_out, task_ids, generator):
       from .. import ops
+      wb, bb = self._value_head0()
       action, logits, baseline = ops.actor_heads_sample(
           core_out.reshape(T * B, -1), self.policy_w, self.policy_b,
-          self.baseline_w, self.baseline_b, generator)
+          wb, bb, generator)
       return AgentOutput(action.view(T, B), logits.view(T, B, -1),
                          baseline.view(T, B)), core_state
     logits, baseline = self.heads(core_out, task_ids)
@@ -559,14 +643,16 @@ class Agent(nn.Module):
       action = None
     return AgentOutput(action, logits, baseline), core_state
 
-  def step(self, last_action, env_output, core_state, generator=None):
-    """Single batched step for actors: inputs [B,...] -> outputs [B,...]."""
+  def step(self, last_action, env_output, core_state, generator=None,
+           epilogue=None):
+    """Single batched step for actors: inputs [B,...] -> outputs [B,...].
+    epilogue: see unroll."""
     exp = lambda t: None if t is None else t.unsqueeze(0)
     reward, info, done, (frame, instr) = env_output
     if instr is not None:
       instr = (instr[0].unsqueeze(0), instr[1].unsqueeze(0))
     eo = (exp(reward), info, exp(done), (exp(frame), instr))
     out, state = self.unroll(exp(last_action), eo, core_state,
-                             generator=generator)
+                             generator=generator, epilogue=epilogue)
     return AgentOutput(out.action[0], out.policy_logits[0],
                        out.baseline[0]), state

@@ -163,6 +163,28 @@ class _CoreLSTM(torch.autograd.Function):
             d_instr, None, None)
 
 
+def core_input_f32(feats, w_fc, b_fc, rewards, actions, num_actions,
+                   instr_enc):
+  """h_aug [N, K] fp32 = [relu(feats W_fc + b_fc), clip(r), one_hot(a),
+  instr|0]: ONE exact-fp32 GEMM (bias + ReLU + the core-input columns in its
+  epilogue) plus the instruction copy.  K = aug_width(A) without
+  instructions; with them the 64 language-LSTM columns join and K is padded
+  to 16 with zero columns (the matching kernel rows - W_h's first rows -
+  meet zeros: no effect)."""
+  f_in = CORE + 1 + num_actions + 64
+  if instr_enc is None:
+    K = aug_width(num_actions)
+  else:
+    K = (f_in + 15) // 16 * 16
+  h_aug = torch.empty(feats.shape[0], K, dtype=torch.float32,
+                      device=feats.device)
+  ext().gemm_f32(feats, w_fc, False, False, h_aug, bias=b_fc, relu=True,
+                 aug_reward=rewards, aug_action=actions)
+  if instr_enc is not None:
+    h_aug[:, f_in - 64:f_in].copy_(instr_enc)
+  return h_aug
+
+
 class _CoreLSTMF32(torch.autograd.Function):
   """Reference-precision (fp32) variant: every product is the exact-fp32
   MFMA GEMM of kernels/gemm_f32.hip with its fused epilogue, the recurrence
@@ -194,17 +216,9 @@ class _CoreLSTMF32(torch.autograd.Function):
     f_in = CORE + 1 + num_actions + 64
     c_instr = CORE + 1 + num_actions
     assert kernel.shape[0] == f_in + CORE
-    if instr_enc is None:
-      K = ld = aug_width(num_actions)
-    else:
-      # instruction columns join; K padded to 16 with zero columns (the
-      # matching kernel rows - W_h's first rows - meet zeros: no effect)
-      K = ld = (f_in + 15) // 16 * 16
-    h_aug = torch.empty(N, ld, dtype=torch.float32, device=feats.device)
-    C.gemm_f32(feats, w_fc, False, False, h_aug, bias=b_fc, relu=True,
-               aug_reward=rewards, aug_action=actions)
-    if instr_enc is not None:
-      h_aug[:, c_instr:f_in].copy_(instr_enc)
+    h_aug = core_input_f32(feats, w_fc, b_fc, rewards, actions, num_actions,
+                           instr_enc)
+    K = h_aug.shape[1]
     xw = torch.empty(N, 4 * CORE, dtype=torch.float32, device=feats.device)
     C.gemm_f32(h_aug, kernel[:K], False, False, xw, bias=bias)
     mode = C.lstm_mode(CORE, B, T, True)  # exact: never the bf16 gang

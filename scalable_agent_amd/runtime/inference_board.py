@@ -264,9 +264,19 @@ class BoardServer(object):
     b = self.board
     _, out_dev, mask_dev, _, dev_in = self._sets[k]
     la, rw, dn, fr, ids, ln = dev_in
+    C = self._epilogue_ext()
+    if C is not None and getattr(self.model, 'actor_core', 'ops') == 'fused':
+      # the fused actor core commits the masked state and packs the outputs
+      # in its own launch: no separate epilogue
+      from ..ops.actor_core import BoardEpilogue
+      self.model.step_device(
+          la, rw, dn, fr, ids, ln, self.c, self.h, has_instr=has_instr,
+          epilogue=BoardEpilogue(mask_dev, [o for _, _, _, o, _ in b.out_fields],
+                                 b.M, b.slot_out_bytes, out_dev,
+                                 self._out_addr))
+      return
     action, logits, baseline, c2, h2 = self.model.step_device(
         la, rw, dn, fr, ids, ln, self.c, self.h, has_instr=has_instr)
-    C = self._epilogue_ext()
     if C is not None:
       # ONE launch for the masked state update and the slot-major output
       # packing (the torch form below is 12 dependent launches, ~57 us of

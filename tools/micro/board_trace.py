@@ -5,8 +5,8 @@
 
 Reads a rocprofv3 --kernel-trace --memory-copy-trace database of an
 `experiment.py` run with the inference board, finds the board's launches by
-their last kernel (actor_head_sample_kernel: the fused heads + sampler ends
-every inference graph) on the inference queue, and prints for the steady
+their sampling kernel (actor_head_sample_kernel, the fused heads + sampler,
+or actor_core_step_kernel with --actor_core=fused) on the inference queue, and prints for the steady
 state (the middle half of the launches): launches per second, the mean time
 from one launch's first kernel to its sampler's end, the GPU-busy part of it,
 the kernels of one launch (name, us) and the copies on the queue.
@@ -16,14 +16,18 @@ import sqlite3
 import sys
 
 
+def _sampler(name):
+  return 'actor_head_sample' in name or 'actor_core_step' in name
+
+
 def main():
   db, out = sys.argv[1], (sys.argv[2] if len(sys.argv) > 2 else None)
   c = sqlite3.connect(db)
   rows = list(c.execute('select name, queue_id, start, end from kernels '
                         'order by start'))
-  samp = [r for r in rows if 'actor_head_sample' in r[0]]
+  samp = [r for r in rows if _sampler(r[0])]
   if not samp:
-    raise SystemExit('no actor_head_sample_kernel in the trace')
+    raise SystemExit('no sampling kernel in the trace')
   q = collections.Counter(r[1] for r in samp).most_common(1)[0][0]
   inf = [r for r in rows if r[1] == q]
   ends = [r[3] for r in samp if r[1] == q]
@@ -32,7 +36,7 @@ def main():
   ei = 0
   for r in inf:
     cur.append(r)
-    if 'actor_head_sample' in r[0]:
+    if _sampler(r[0]):
       launches.append(cur)
       cur = []
   n = len(launches)
