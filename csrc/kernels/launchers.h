@@ -138,17 +138,22 @@ struct HeadTasks {
   const float* nu = nullptr;
   float* vs_out = nullptr;
 };
+// learner_head_fwd_smem: the dynamic LDS bytes of an unroll of T steps;
+// learner_head_fwd_max_unroll: the largest T at which they fit a workgroup's
+// LDS together with the kernel's static arrays.  The launch returns the
+// runtime's error (an inadmissible T: hipErrorInvalidValue, nothing launched).
 size_t learner_head_fwd_smem(int T, int A);
-void learner_head_fwd_launch(const float* core, const float* wp, const float* bp,
-                             const float* wb, const float* bb,
-                             const float* behaviour, const int64_t* actions,
-                             const float* rewards, const uint8_t* done, int T,
-                             int B, int A, float discounting, int clip_mode,
-                             float clip_rho, float clip_pg_rho,
-                             float baseline_cost, float entropy_cost,
-                             float* dlogits, float* dvalues, float* partial,
-                             unsigned* ticket, float* loss, const HeadTasks& tk,
-                             hipStream_t stream);
+int learner_head_fwd_max_unroll(int A);
+hipError_t learner_head_fwd_launch(const float* core, const float* wp, const float* bp,
+                                   const float* wb, const float* bb,
+                                   const float* behaviour, const int64_t* actions,
+                                   const float* rewards, const uint8_t* done, int T,
+                                   int B, int A, float discounting, int clip_mode,
+                                   float clip_rho, float clip_pg_rho,
+                                   float baseline_cost, float entropy_cost,
+                                   float* dlogits, float* dvalues, float* partial,
+                                   unsigned* ticket, float* loss, const HeadTasks& tk,
+                                   hipStream_t stream);
 // dcore [N1,256] = g (dlogits Wp^T + dv Wb[:, task]^T) (rows >= Ng zero;
 // row r = t B + b reads head task[r % B], task null = head 0); heads'
 // gradients accumulated into gwp [256,A], gbp [A], gwb [256,K], gbb [K]

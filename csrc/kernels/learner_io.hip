@@ -76,6 +76,12 @@ constexpr float kPopArtSigmaMin = 1e-4f;
 constexpr float kPopArtSigmaMax = 1e6f;
 constexpr int kHeadWaves = kHeadThreads / 64;
 constexpr int kMaxA = 31;      // A + 1 head outputs <= 32
+// LDS of one workgroup: learner_head_fwd's dynamic arrays and its static ones
+// (scan_a, scan_b, red, last_s; kHeadStaticLds bounds them, asserted next to
+// their declarations) must fit together
+constexpr size_t kLdsPerWorkgroup = 160 * 1024;
+constexpr size_t kHeadStaticLds =
+    sizeof(float) * (2 * kHeadThreads + 3 * kHeadWaves) + 16;
 
 // ------------------------------------------------------------ heads + V-trace
 // core [T1,B,H] (H == 256), Wp [H,A], Wb [H] (one value head).  The V-trace
@@ -118,6 +124,10 @@ __global__ __launch_bounds__(kHeadThreads) void learner_head_fwd_kernel(
   __shared__ float scan_a[kHeadThreads], scan_b[kHeadThreads];
   __shared__ float red[3][kHeadWaves];
   __shared__ bool last_s;
+  // four naturally aligned arrays: at most 3 bytes of padding in total
+  static_assert(sizeof(scan_a) + sizeof(scan_b) + sizeof(red) + sizeof(last_s) + 3 <=
+                    kHeadStaticLds,
+                "kHeadStaticLds must cover the static LDS of learner_head_fwd");
   const int b = blockIdx.x;
   const int tid = threadIdx.x;
   const int lane = tid & 63;
@@ -674,29 +684,41 @@ size_t learner_head_fwd_smem(int T, int A) {
                           1 + 3 * T);
 }
 
-void learner_head_fwd_launch(const float* core, const float* wp, const float* bp,
-                             const float* wb, const float* bb,
-                             const float* behaviour, const int64_t* actions,
-                             const float* rewards, const uint8_t* done, int T,
-                             int B, int A, float discounting, int clip_mode,
-                             float clip_rho, float clip_pg_rho,
-                             float baseline_cost, float entropy_cost,
-                             float* dlogits, float* dvalues, float* partial,
-                             unsigned* ticket, float* loss, const HeadTasks& tk,
-                             hipStream_t stream) {
+int learner_head_fwd_max_unroll(int A) {
+  // smem(T, A) is affine in T: the largest T whose dynamic + static LDS fits
+  const size_t base = learner_head_fwd_smem(0, A);
+  const size_t per_step = learner_head_fwd_smem(1, A) - base;
+  if (base + kHeadStaticLds > kLdsPerWorkgroup) return 0;
+  return static_cast<int>((kLdsPerWorkgroup - kHeadStaticLds - base) / per_step);
+}
+
+hipError_t learner_head_fwd_launch(const float* core, const float* wp, const float* bp,
+                                   const float* wb, const float* bb,
+                                   const float* behaviour, const int64_t* actions,
+                                   const float* rewards, const uint8_t* done, int T,
+                                   int B, int A, float discounting, int clip_mode,
+                                   float clip_rho, float clip_pg_rho,
+                                   float baseline_cost, float entropy_cost,
+                                   float* dlogits, float* dvalues, float* partial,
+                                   unsigned* ticket, float* loss, const HeadTasks& tk,
+                                   hipStream_t stream) {
+  if (T < 1 || T > learner_head_fwd_max_unroll(A)) return hipErrorInvalidValue;
   const size_t smem = learner_head_fwd_smem(T, A);
   auto k16 = learner_head_fwd_kernel<16>;
   auto k32 = learner_head_fwd_kernel<kMaxA + 1>;
   auto kern = (A + 1 <= 16) ? k16 : k32;
-  if (smem > 64 * 1024)
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                              hipFuncAttributeMaxDynamicSharedMemorySize,
-                              static_cast<int>(smem));
+  if (smem > 64 * 1024) {
+    const hipError_t e = hipFuncSetAttribute(
+        reinterpret_cast<const void*>(kern),
+        hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(smem));
+    if (e != hipSuccess) return e;
+  }
   hipLaunchKernelGGL(kern, dim3(B), dim3(kHeadThreads), smem, stream, core, wp,
                      bp, wb, bb, behaviour, actions, rewards, done, T, B, A,
                      discounting, clip_mode, clip_rho, clip_pg_rho,
                      baseline_cost, entropy_cost, dlogits, dvalues, partial,
                      ticket, loss, tk);
+  return hipGetLastError();
 }
 
 int head_bwd_maxc(int A1) { return A1 <= 16 ? 16 : (A1 <= 32 ? 32 : 64); }

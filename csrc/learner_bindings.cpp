@@ -58,7 +58,8 @@ std::vector<at::Tensor> learner_head_fwd(
   TORCH_CHECK(behaviour.numel() == (int64_t)T1 * B * A, "behaviour logits shape");
   TORCH_CHECK(actions.numel() == (int64_t)T1 * B && rewards.numel() == (int64_t)T1 * B &&
               done.numel() == (int64_t)T1 * B, "[T+1,B] shape mismatch");
-  TORCH_CHECK(sa::learner_head_fwd_smem(T, A) <= 160 * 1024, "unroll too long");
+  TORCH_CHECK(T <= sa::learner_head_fwd_max_unroll(A), "unroll too long: T = ", T,
+              " > ", sa::learner_head_fwd_max_unroll(A), " steps fit the LDS at A = ", A);
   sa::HeadTasks tk;
   tk.K = K;
   if (task.has_value()) {
@@ -83,7 +84,7 @@ std::vector<at::Tensor> learner_head_fwd(
     vs = at::empty({T, B}, f32);
     tk.vs_out = vs.data_ptr<float>();
   }
-  sa::learner_head_fwd_launch(
+  const hipError_t err = sa::learner_head_fwd_launch(
       core.data_ptr<float>(), wp.data_ptr<float>(), bp.data_ptr<float>(),
       wb.data_ptr<float>(), bb.data_ptr<float>(),
       behaviour.data_ptr<float>() + (int64_t)B * A,
@@ -93,6 +94,7 @@ std::vector<at::Tensor> learner_head_fwd(
       (float)entropy_cost, dlogits.data_ptr<float>(), dvalues.data_ptr<float>(),
       partial.data_ptr<float>(), reinterpret_cast<unsigned*>(ticket.data_ptr<int>()),
       loss.data_ptr<float>(), tk, stream());
+  TORCH_CHECK(err == hipSuccess, "learner_head_fwd launch failed: ", hipGetErrorString(err));
   if (want_vs) return {loss, dlogits, dvalues, vs};
   return {loss, dlogits, dvalues};
 }
@@ -610,6 +612,10 @@ std::vector<at::Tensor> lang_lstm_bwd(at::Tensor lengths, at::Tensor kernel, at:
 }  // namespace
 
 void register_learner_ops(pybind11::module& m) {
+  m.def("learner_head_max_unroll", [](int64_t A) {
+    TORCH_CHECK(A >= 1 && A + 1 <= 32, "1 <= num_actions <= 31");
+    return (int64_t)sa::learner_head_fwd_max_unroll((int)A);
+  }, pybind11::arg("num_actions"));
   m.def("learner_head_fwd", &learner_head_fwd, pybind11::arg("core"), pybind11::arg("wp"),
         pybind11::arg("bp"), pybind11::arg("wb"), pybind11::arg("bb"),
         pybind11::arg("behaviour"), pybind11::arg("actions"), pybind11::arg("rewards"),

@@ -33,6 +33,13 @@ def _ticket(device):
   return t
 
 
+def learner_head_max_unroll(num_actions):
+  """Largest unroll length T the fused heads kernel takes at this action
+  count: its per-column working set (dynamic and static LDS) has to fit one
+  workgroup.  heads_vtrace_loss raises RuntimeError above it."""
+  return int(ext().learner_head_max_unroll(int(num_actions)))
+
+
 class _HeadsVTraceLoss(torch.autograd.Function):
 
   @staticmethod
