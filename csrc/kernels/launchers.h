@@ -154,6 +154,24 @@ hipError_t learner_head_fwd_launch(const float* core, const float* wp, const flo
                                    float* dlogits, float* dvalues, float* partial,
                                    unsigned* ticket, float* loss, const HeadTasks& tk,
                                    hipStream_t stream);
+// The time-tiled variant: same operands and results for any T and A <= 63.
+// The column is walked in tiles of `time_tile` steps (a multiple of 16 in
+// [16, 1024]) from the end of the unroll, so the LDS
+// (learner_head_fwd_tiled_smem bytes + the static arrays) depends on the tile
+// and not on T.  learner_head_tile_auto: the default tile at A actions.  The
+// launch returns hipErrorInvalidValue (nothing launched) for an inadmissible
+// A / tile or a tile that does not fit the LDS.
+size_t learner_head_fwd_tiled_smem(int time_tile, int A);
+bool learner_head_fwd_tiled_fits(int time_tile, int A);
+int learner_head_tile_auto(int A);
+hipError_t learner_head_fwd_tiled_launch(
+    const float* core, const float* wp, const float* bp, const float* wb,
+    const float* bb, const float* behaviour, const int64_t* actions,
+    const float* rewards, const uint8_t* done, int T, int B, int A,
+    float discounting, int clip_mode, float clip_rho, float clip_pg_rho,
+    float baseline_cost, float entropy_cost, float* dlogits, float* dvalues,
+    float* partial, unsigned* ticket, float* loss, const HeadTasks& tk,
+    int time_tile, hipStream_t stream);
 // dcore [N1,256] = g (dlogits Wp^T + dv Wb[:, task]^T) (rows >= Ng zero;
 // row r = t B + b reads head task[r % B], task null = head 0); heads'
 // gradients accumulated into gwp [256,A], gbp [A], gwb [256,K], gbb [K]

@@ -16,6 +16,11 @@
 //                      sigma n + mu, the baseline error is (vs - mu) / sigma - n
 //                      and the policy-gradient advantage is divided by sigma;
 //                      the targets vs go out for the statistics update.
+//  * learner_head_fwd_tiled  the same column computation in time tiles
+//                      walked from the end of the unroll with the V-trace
+//                      accumulator carried between them: LDS bounded by the
+//                      tile, so any unroll length and up to 63 actions (a
+//                      64-column W image); same ticket, same outputs.
 //  * learner_head_bwd  dcore = g (dlogits W_p^T + dv W_b[:, task]^T) and the
 //                      heads' weight/bias gradients (per-row-chunk slots
 //                      summed in a fixed order), g = the incoming loss
@@ -401,6 +406,304 @@ __global__ __launch_bounds__(kHeadThreads) void learner_head_fwd_kernel(
   HEAD_TRACE(8);
 }
 
+// -------------------------------------------------- heads + V-trace, time-tiled
+// The same column computation with LDS bounded by a time tile of TC steps
+// instead of by T, for unrolls past learner_head_fwd_max_unroll and for
+// A + 1 up to 64 head columns.  The V-trace recursion runs backward in time
+// with a scalar carry, so the column is walked in tiles [c0, c1) of TC steps
+// from the END of the unroll (the tile at t = 0 takes the remainder).  Per
+// tile: heads of rows c0 .. c1 (row c1 gives v_{t+1} of the tile's last step:
+// the bootstrap row T in the first tile, recomputed otherwise), the V-trace
+// terms, the reverse scan seeded with the carried acc_{c1}, then vs, the
+// advantages (vs_{c1} carried; the bootstrap value in the first tile), the
+// loss terms and gradients.  acc_{c0} / vs_{c0} go to the next tile through
+// carry_s.  TC <= kHeadThreads: one step per thread and tile.  The loss
+// partial sums stay in registers over all tiles and are reduced once.  Every
+// barrier is reached by all threads in every tile.  LDS (dynamic, 4-byte
+// words): W [H][MAXC] + 64 | logits/values [TC+1][A+1] | behaviour [TC][A] |
+// a_t, delta_t, pgrho_t, reward, action, discount [TC] | vs_t [TC+1] (2 TC
+// words reserved).
+template <int MAXC>
+__global__ __launch_bounds__(kHeadThreads) void learner_head_fwd_tiled_kernel(
+    const float* __restrict__ core, const float* __restrict__ wp,
+    const float* __restrict__ bp, const float* __restrict__ wb,
+    const float* __restrict__ bb, const float* __restrict__ behaviour,
+    const int64_t* __restrict__ actions, const float* __restrict__ rewards,
+    const uint8_t* __restrict__ done, int T, int B, int A, float discounting,
+    int clip_mode, float clip_rho, float clip_pg_rho, float baseline_cost,
+    float entropy_cost, float* __restrict__ dlogits, float* __restrict__ dvalues,
+    float* __restrict__ partial, unsigned* __restrict__ ticket,
+    float* __restrict__ loss, HeadTasks tk, int TC) {
+  constexpr int H = 256;
+  extern __shared__ float smem[];
+  const int A1 = A + 1;
+  float* w_s = smem;                      // [H][MAXC] + 4 x 16 pad
+  float* lv_s = w_s + H * MAXC + 64;      // [TC+1][A1]: logits then value
+  float* beh_s = lv_s + (TC + 1) * A1;    // [TC][A]
+  float* a_s = beh_s + TC * A;            // gamma_t c_t
+  float* d_s = a_s + TC;                  // delta_t
+  float* p_s = d_s + TC;                  // clipped pg rho
+  float* r_s = p_s + TC;                  // clipped reward
+  int* act_s = reinterpret_cast<int*>(r_s + TC);
+  float* disc_s = reinterpret_cast<float*>(act_s + TC);
+  float* vs_s = disc_s + TC;              // vs_t, vs_s[n] = vs_{c1}
+  __shared__ float scan_a[kHeadThreads], scan_b[kHeadThreads];
+  __shared__ float red[3][kHeadWaves];
+  __shared__ float carry_s[2];            // acc_{c0}, vs_{c0} of the last tile
+  __shared__ bool last_s;
+  static_assert(sizeof(scan_a) + sizeof(scan_b) + sizeof(red) + sizeof(carry_s) +
+                        sizeof(last_s) + 3 <= kHeadStaticLds,
+                "kHeadStaticLds must cover the static LDS of learner_head_fwd_tiled");
+  const int b = blockIdx.x;
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int wave = tid >> 6;
+  // value head and PopArt statistics of the column, as learner_head_fwd (a
+  // bad task id: head 0 with a NaN sigma)
+  const int64_t kt_raw = tk.task != nullptr ? tk.task[b] : 0;
+  const bool kt_bad = kt_raw < 0 || kt_raw >= tk.K;
+  const int kt = kt_bad ? 0 : static_cast<int>(kt_raw);
+  float sig = 1.f, mu = 0.f;
+  if (tk.mu != nullptr) {
+    mu = tk.mu[kt];
+    const float var = fmaxf(tk.nu[kt] - mu * mu, kPopArtSigmaMin * kPopArtSigmaMin);
+    sig = fminf(fmaxf(sqrtf(var), kPopArtSigmaMin), kPopArtSigmaMax);
+  }
+  if (kt_bad) sig = __builtin_nanf("");
+  const float rsig = 1.f / sig;
+
+  // ---- W image, once per column (the layout of learner_head_fwd)
+  constexpr int NCT = MAXC / 16;  // 16-wide output column tiles
+  const int arow = lane & 15, kq = lane >> 4;
+  float bias[NCT];
+#pragma unroll
+  for (int ct = 0; ct < NCT; ++ct) {
+    const int c = 16 * ct + arow;
+    bias[ct] = c < A ? bp[c] : (c == A ? bb[kt] : 0.f);
+  }
+  constexpr int WPT = H * MAXC / kHeadThreads;
+  float wv[WPT];
+#pragma unroll
+  for (int j = 0; j < WPT; ++j) {
+    const int i = tid + j * kHeadThreads;
+    const int k = i / MAXC, c = i - k * MAXC;
+    wv[j] = c < A ? wp[k * A + c] : (c == A ? wb[k * tk.K + kt] : 0.f);
+  }
+#pragma unroll
+  for (int j = 0; j < WPT; ++j) {
+    const int i = tid + j * kHeadThreads;
+    w_s[i + 16 * ((i / MAXC) >> 6)] = wv[j];
+  }
+  if (tid == 0) {
+    carry_s[0] = 0.f;  // acc_T
+    carry_s[1] = 0.f;  // (the first tile takes the bootstrap value instead)
+  }
+
+  float l_pg = 0.f, l_bl = 0.f, l_ent = 0.f;
+  const int ntt = (T + TC - 1) / TC;
+  for (int tt = 0; tt < ntt; ++tt) {
+    const int c1 = T - tt * TC;
+    const int c0 = max(c1 - TC, 0);
+    const int n = c1 - c0;             // steps of this tile, 1 <= n <= TC
+    const int nrt = (n + 1 + 15) / 16;  // 16-row head tiles over rows c0 .. c1
+    const bool on = tid < n;           // this thread's step: t = c0 + tid
+    // A operand, one half of the lane's 64 k at a time (1024 threads: 128
+    // registers a lane): core[c0 + 16 tile + arow][64 kq + 32 h + 4j .. +3]
+    float4 xa[8];
+    auto load_a = [&](int tile, int h) {
+      const int i = 16 * tile + arow;
+      const float4* src = reinterpret_cast<const float4*>(
+          core + (static_cast<int64_t>(i <= n ? c0 + i : 0) * B + b) * H + 64 * kq +
+          32 * h);
+#pragma unroll
+      for (int j = 0; j < 8; ++j) xa[j] = i <= n ? src[j] : float4{0.f, 0.f, 0.f, 0.f};
+    };
+    if (wave < nrt) load_a(wave, 0);
+    // W staged (first tile) / the previous tile's readers are done
+    __syncthreads();
+    const float acc_in = carry_s[0], vs_in = carry_s[1];
+    for (int i = tid; i < n * A; i += kHeadThreads) {
+      const int t = i / A, jj = i - t * A;
+      beh_s[i] = behaviour[(static_cast<int64_t>(c0 + t) * B + b) * A + jj];
+    }
+    if (on) {
+      const int64_t idx = static_cast<int64_t>(c0 + tid) * B + b;  // row t+1 of batch
+      r_s[tid] = clip_reward(rewards[idx], clip_mode);
+      act_s[tid] = static_cast<int>(actions[idx]);
+      disc_s[tid] = done[idx] ? 0.f : discounting;
+    }
+
+    // ---- heads of rows c0 .. c1: [16 rows x 256] x [256 x 16 cols] per wave
+    for (int tile = wave; tile < nrt; tile += kHeadWaves) {
+      f4v acc[NCT];
+#pragma unroll
+      for (int ct = 0; ct < NCT; ++ct) acc[ct] = f4v{0.f, 0.f, 0.f, 0.f};
+#pragma unroll 1
+      for (int h = 0; h < 2; ++h) {
+        if (tile != wave || h != 0) load_a(tile, h);
+        const float* wk = w_s + (64 * kq + 32 * h) * MAXC + 16 * kq + arow;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+          const float av[4] = {xa[j].x, xa[j].y, xa[j].z, xa[j].w};
+#pragma unroll
+          for (int q = 0; q < 4; ++q) {
+#pragma unroll
+            for (int ct = 0; ct < NCT; ++ct)
+              acc[ct] = __builtin_amdgcn_mfma_f32_16x16x4f32(
+                  av[q], wk[(4 * j + q) * MAXC + 16 * ct], acc[ct], 0, 0, 0);
+          }
+        }
+      }
+      // D[row 4 kq + i][col arow]
+#pragma unroll
+      for (int ct = 0; ct < NCT; ++ct) {
+        const int c = 16 * ct + arow;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          const int row = 16 * tile + 4 * kq + i;
+          if (row <= n && c < A1) lv_s[row * A1 + c] = acc[ct][i] + bias[ct];
+        }
+      }
+    }
+    __syncthreads();
+
+    // ---- V-trace elementwise (vtrace.py:143-147, 235-262)
+    if (on) {
+      const float* zt = lv_s + tid * A1;
+      const float* zb = beh_s + tid * A;
+      const int a = act_s[tid];
+      float mt = -INFINITY, mb = -INFINITY;
+      for (int j = 0; j < A; ++j) {
+        mt = fmaxf(mt, zt[j]);
+        mb = fmaxf(mb, zb[j]);
+      }
+      float st = 0.f, sb = 0.f;
+      for (int j = 0; j < A; ++j) {
+        st += __expf(zt[j] - mt);
+        sb += __expf(zb[j] - mb);
+      }
+      const float log_pi = zt[a] - mt - __logf(st);
+      const float log_mu = zb[a] - mb - __logf(sb);
+      const float rho = __expf(log_pi - log_mu);
+      const float disc = disc_s[tid];
+      const float v = sig * zt[A] + mu;  // de-normalised (PopArt) values
+      const float v1 = sig * lv_s[(tid + 1) * A1 + A] + mu;
+      a_s[tid] = disc * fminf(1.0f, rho);
+      d_s[tid] = fminf(clip_rho, rho) * (r_s[tid] + disc * v1 - v);
+      p_s[tid] = fminf(clip_pg_rho, rho);
+    }
+    __syncthreads();
+
+    // ---- reverse recursion acc_t = delta_t + a_t acc_{t+1} over the tile:
+    // a workgroup suffix scan of the per-step maps (identity past the tile's
+    // end), entered from the right with the carried acc_{c1}
+    float ca = on ? a_s[tid] : 1.f;  // acc_t = cb + ca * acc_{t+1}
+    float cb = on ? d_s[tid] : 0.f;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {  // wave-level inclusive suffix
+      const float na = __shfl_down(ca, d, 64);
+      const float nb = __shfl_down(cb, d, 64);
+      if (lane + d < 64) {
+        cb = cb + ca * nb;
+        ca = ca * na;
+      }
+    }
+    scan_a[tid] = ca;
+    scan_b[tid] = cb;
+    __syncthreads();
+    float acc = acc_in;
+    for (int w = kHeadWaves - 1; w > wave; --w) acc = scan_b[w * 64] + scan_a[w * 64] * acc;
+    if (lane < 63) acc = scan_b[tid + 1] + scan_a[tid + 1] * acc;
+    if (on) {
+      acc = d_s[tid] + a_s[tid] * acc;
+      const float vs = acc + (sig * lv_s[tid * A1 + A] + mu);
+      vs_s[tid] = vs;
+      if (tid == 0) {  // t = c0: the next tile's c1
+        carry_s[0] = acc;
+        carry_s[1] = vs;
+      }
+    }
+    if (tid == 0) vs_s[n] = tt == 0 ? sig * lv_s[n * A1 + A] + mu : vs_in;
+    __syncthreads();
+
+    // ---- advantages, loss terms and their gradients
+    if (on) {
+      const int64_t idx = static_cast<int64_t>(c0 + tid) * B + b;
+      const float* zt = lv_s + tid * A1;
+      float* dz = dlogits + idx * A;
+      const int a = act_s[tid];
+      const float nv = zt[A];
+      const float v = sig * nv + mu;
+      const float vs = vs_s[tid];
+      // PopArt: advantages in normalised units, baseline error against the
+      // normalised target (sig = 1, mu = 0: the plain IMPALA loss)
+      const float pg_adv = p_s[tid] * (r_s[tid] + disc_s[tid] * vs_s[tid + 1] - v) * rsig;
+      const float err = (vs - mu) * rsig - nv;
+      if (tk.vs_out != nullptr) tk.vs_out[idx] = vs;
+      float m = -INFINITY;
+      for (int j = 0; j < A; ++j) m = fmaxf(m, zt[j]);
+      float s = 0.f;
+      for (int j = 0; j < A; ++j) s += __expf(zt[j] - m);
+      const float lse = m + __logf(s);
+      float Hn = 0.f;
+      for (int j = 0; j < A; ++j) {
+        const float lp = zt[j] - lse;
+        Hn -= __expf(lp) * lp;
+      }
+      for (int j = 0; j < A; ++j) {
+        const float lp = zt[j] - lse;
+        const float p = __expf(lp);
+        dz[j] = (p - (j == a ? 1.f : 0.f)) * pg_adv + entropy_cost * p * (lp + Hn);
+      }
+      dvalues[idx] = -baseline_cost * err;
+      l_pg += (lse - zt[a]) * pg_adv;
+      l_bl += 0.5f * err * err;
+      l_ent -= Hn;
+    }
+  }
+
+  // ---- the column's loss sums, then the last workgroup's fixed-order total
+  // (the hand-off of learner_head_fwd: sc1 partials, one ticket, re-armed)
+  l_pg = wave_sum(l_pg);
+  l_bl = wave_sum(l_bl);
+  l_ent = wave_sum(l_ent);
+  if (lane == 0) {
+    red[0][wave] = l_pg;
+    red[1][wave] = l_bl;
+    red[2][wave] = l_ent;
+  }
+  __syncthreads();
+  if (tid == 0) {
+    float pg = 0.f, bl = 0.f, en = 0.f;
+    for (int w = 0; w < kHeadWaves; ++w) {
+      pg += red[0][w];
+      bl += red[1][w];
+      en += red[2][w];
+    }
+    __hip_atomic_store(partial + b * 3 + 0, pg, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_store(partial + b * 3 + 1, bl, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_store(partial + b * 3 + 2, en, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    const unsigned prev = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED,
+                                                 __HIP_MEMORY_SCOPE_AGENT);
+    last_s = (prev == static_cast<unsigned>(gridDim.x) - 1);
+  }
+  __syncthreads();
+  if (last_s && tid == 0) {
+    float pg = 0.f, bl = 0.f, en = 0.f;
+    for (int j = 0; j < B; ++j) {  // fixed order: deterministic
+      pg += __hip_atomic_load(partial + j * 3 + 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      bl += __hip_atomic_load(partial + j * 3 + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      en += __hip_atomic_load(partial + j * 3 + 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    loss[1] = pg;
+    loss[2] = bl;
+    loss[3] = en;
+    loss[0] = pg + baseline_cost * bl + entropy_cost * en;
+    __hip_atomic_store(ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // next launch
+  }
+}
+
 // dcore [N1, H] = g (dlogits W_p^T + dv W_b[:, task]^T) (rows >= Ng get
 // zero), and g core^T [dlogits | dv routed to the row's value head] and its
 // column sums into per-row-chunk slots.  Columns: c < A policy, A + k value
@@ -718,6 +1021,65 @@ hipError_t learner_head_fwd_launch(const float* core, const float* wp, const flo
                      discounting, clip_mode, clip_rho, clip_pg_rho,
                      baseline_cost, entropy_cost, dlogits, dvalues, partial,
                      ticket, loss, tk);
+  return hipGetLastError();
+}
+
+namespace {
+constexpr int kTiledMaxA = 63;  // A + 1 head outputs <= 64
+int head_tiled_maxc(int A) { return A + 1 <= 16 ? 16 : (A + 1 <= 32 ? 32 : 64); }
+bool head_tile_ok(int tc) { return tc >= 16 && tc <= kHeadThreads && tc % 16 == 0; }
+}  // namespace
+
+size_t learner_head_fwd_tiled_smem(int TC, int A) {
+  return sizeof(float) * (256 * head_tiled_maxc(A) + 64 +
+                          static_cast<size_t>(TC + 1) * (A + 1) +
+                          static_cast<size_t>(TC) * A + 8 * static_cast<size_t>(TC));
+}
+
+bool learner_head_fwd_tiled_fits(int TC, int A) {
+  return learner_head_fwd_tiled_smem(TC, A) + kHeadStaticLds <= kLdsPerWorkgroup;
+}
+
+int learner_head_tile_auto(int A) {
+  // The largest tile that fits the LDS: the fewest tiles per column.  With one
+  // column per workgroup and B far below the CU count a second workgroup per
+  // CU buys nothing, while every tile pays its barriers, the recomputed row
+  // c1 and a partly filled heads pass; measured on MI355X in
+  // profiles/experiments.md ("Time-tiled learner heads").
+  int best = 16;
+  for (int tc = 16; tc <= kHeadThreads; tc += 16)
+    if (learner_head_fwd_tiled_fits(tc, A)) best = tc;
+  return best;
+}
+
+hipError_t learner_head_fwd_tiled_launch(
+    const float* core, const float* wp, const float* bp, const float* wb,
+    const float* bb, const float* behaviour, const int64_t* actions,
+    const float* rewards, const uint8_t* done, int T, int B, int A,
+    float discounting, int clip_mode, float clip_rho, float clip_pg_rho,
+    float baseline_cost, float entropy_cost, float* dlogits, float* dvalues,
+    float* partial, unsigned* ticket, float* loss, const HeadTasks& tk,
+    int time_tile, hipStream_t stream) {
+  if (T < 1 || B < 1 || A < 1 || A > kTiledMaxA || !head_tile_ok(time_tile) ||
+      !learner_head_fwd_tiled_fits(time_tile, A))
+    return hipErrorInvalidValue;
+  const size_t smem = learner_head_fwd_tiled_smem(time_tile, A);
+  auto k16 = learner_head_fwd_tiled_kernel<16>;
+  auto k32 = learner_head_fwd_tiled_kernel<32>;
+  auto k64 = learner_head_fwd_tiled_kernel<64>;
+  const int maxc = head_tiled_maxc(A);
+  auto kern = maxc == 16 ? k16 : (maxc == 32 ? k32 : k64);
+  if (smem > 64 * 1024) {
+    const hipError_t e = hipFuncSetAttribute(
+        reinterpret_cast<const void*>(kern),
+        hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(smem));
+    if (e != hipSuccess) return e;
+  }
+  hipLaunchKernelGGL(kern, dim3(B), dim3(kHeadThreads), smem, stream, core, wp,
+                     bp, wb, bb, behaviour, actions, rewards, done, T, B, A,
+                     discounting, clip_mode, clip_rho, clip_pg_rho,
+                     baseline_cost, entropy_cost, dlogits, dvalues, partial,
+                     ticket, loss, tk, time_tile);
   return hipGetLastError();
 }
 

@@ -29,13 +29,16 @@ const uint8_t* mask_ptr(const at::Tensor& t) {
 // task [B] (int64 head per batch column; required when K > 1); PopArt:
 // mu / nu [K] statistics (both or neither), want_vs returns the V-trace
 // targets.  -> {loss[4], dlogits [T,B,A], dvalues [T,B][, vs [T,B]]}
-std::vector<at::Tensor> learner_head_fwd(
+// time_tile < 0: learner_head_fwd (T bounded by the LDS, A <= 31); otherwise
+// the time-tiled kernel (any T, A <= 63) with tiles of time_tile steps.
+std::vector<at::Tensor> head_fwd_impl(
     at::Tensor core, at::Tensor wp, at::Tensor bp, at::Tensor wb, at::Tensor bb,
     at::Tensor behaviour, at::Tensor actions, at::Tensor rewards, at::Tensor done,
     at::Tensor ticket, double discounting, int64_t clip_mode, double clip_rho,
     double clip_pg_rho, double baseline_cost, double entropy_cost,
     c10::optional<at::Tensor> task, c10::optional<at::Tensor> mu,
-    c10::optional<at::Tensor> nu, bool want_vs) {
+    c10::optional<at::Tensor> nu, bool want_vs, int64_t time_tile) {
+  const bool tiled = time_tile >= 0;
   LB_CHECK(core); LB_CHECK(wp); LB_CHECK(bp); LB_CHECK(wb); LB_CHECK(bb);
   LB_CHECK(behaviour); LB_CHECK(actions); LB_CHECK(rewards); LB_CHECK(done);
   LB_CHECK(ticket);
@@ -48,7 +51,11 @@ std::vector<at::Tensor> learner_head_fwd(
   const int A = wp.size(1);
   TORCH_CHECK(T >= 1, "need T >= 1");
   TORCH_CHECK(wp.dim() == 2 && wp.size(0) == 256, "policy w must be [256,A]");
-  TORCH_CHECK(A >= 1 && A + 1 <= 32, "1 <= num_actions <= 31");
+  if (tiled) {
+    TORCH_CHECK(A >= 1 && A + 1 <= 64, "1 <= num_actions <= 63");
+  } else {
+    TORCH_CHECK(A >= 1 && A + 1 <= 32, "1 <= num_actions <= 31");
+  }
   TORCH_CHECK(wb.numel() % 256 == 0, "value w must be [256, K]");
   const int K = wb.numel() / 256;
   TORCH_CHECK(bp.numel() == A && bb.numel() == K && K >= 1 && A + K <= 64,
@@ -58,8 +65,18 @@ std::vector<at::Tensor> learner_head_fwd(
   TORCH_CHECK(behaviour.numel() == (int64_t)T1 * B * A, "behaviour logits shape");
   TORCH_CHECK(actions.numel() == (int64_t)T1 * B && rewards.numel() == (int64_t)T1 * B &&
               done.numel() == (int64_t)T1 * B, "[T+1,B] shape mismatch");
-  TORCH_CHECK(T <= sa::learner_head_fwd_max_unroll(A), "unroll too long: T = ", T,
-              " > ", sa::learner_head_fwd_max_unroll(A), " steps fit the LDS at A = ", A);
+  if (tiled) {
+    TORCH_CHECK(time_tile >= 16 && time_tile <= 1024 && time_tile % 16 == 0,
+                "time_tile must be a multiple of 16 in [16, 1024], got ", time_tile);
+    TORCH_CHECK(sa::learner_head_fwd_tiled_fits((int)time_tile, A),
+                "time_tile too large: ", time_tile, " steps need ",
+                sa::learner_head_fwd_tiled_smem((int)time_tile, A),
+                " bytes of dynamic LDS at A = ", A,
+                ", more than a workgroup has next to the kernel's static arrays");
+  } else {
+    TORCH_CHECK(T <= sa::learner_head_fwd_max_unroll(A), "unroll too long: T = ", T,
+                " > ", sa::learner_head_fwd_max_unroll(A), " steps fit the LDS at A = ", A);
+  }
   sa::HeadTasks tk;
   tk.K = K;
   if (task.has_value()) {
@@ -84,19 +101,57 @@ std::vector<at::Tensor> learner_head_fwd(
     vs = at::empty({T, B}, f32);
     tk.vs_out = vs.data_ptr<float>();
   }
-  const hipError_t err = sa::learner_head_fwd_launch(
-      core.data_ptr<float>(), wp.data_ptr<float>(), bp.data_ptr<float>(),
-      wb.data_ptr<float>(), bb.data_ptr<float>(),
-      behaviour.data_ptr<float>() + (int64_t)B * A,
-      actions.data_ptr<int64_t>() + B, rewards.data_ptr<float>() + B,
-      mask_ptr(done) + B, T, B, A, (float)discounting, (int)clip_mode,
-      (float)clip_rho, (float)clip_pg_rho, (float)baseline_cost,
-      (float)entropy_cost, dlogits.data_ptr<float>(), dvalues.data_ptr<float>(),
-      partial.data_ptr<float>(), reinterpret_cast<unsigned*>(ticket.data_ptr<int>()),
-      loss.data_ptr<float>(), tk, stream());
-  TORCH_CHECK(err == hipSuccess, "learner_head_fwd launch failed: ", hipGetErrorString(err));
+  const float* beh1 = behaviour.data_ptr<float>() + (int64_t)B * A;
+  const int64_t* act1 = actions.data_ptr<int64_t>() + B;
+  const float* rew1 = rewards.data_ptr<float>() + B;
+  const uint8_t* done1 = mask_ptr(done) + B;
+  unsigned* tick = reinterpret_cast<unsigned*>(ticket.data_ptr<int>());
+  const hipError_t err = tiled
+      ? sa::learner_head_fwd_tiled_launch(
+            core.data_ptr<float>(), wp.data_ptr<float>(), bp.data_ptr<float>(),
+            wb.data_ptr<float>(), bb.data_ptr<float>(), beh1, act1, rew1, done1, T,
+            B, A, (float)discounting, (int)clip_mode, (float)clip_rho,
+            (float)clip_pg_rho, (float)baseline_cost, (float)entropy_cost,
+            dlogits.data_ptr<float>(), dvalues.data_ptr<float>(),
+            partial.data_ptr<float>(), tick, loss.data_ptr<float>(), tk,
+            (int)time_tile, stream())
+      : sa::learner_head_fwd_launch(
+            core.data_ptr<float>(), wp.data_ptr<float>(), bp.data_ptr<float>(),
+            wb.data_ptr<float>(), bb.data_ptr<float>(), beh1, act1, rew1, done1, T,
+            B, A, (float)discounting, (int)clip_mode, (float)clip_rho,
+            (float)clip_pg_rho, (float)baseline_cost, (float)entropy_cost,
+            dlogits.data_ptr<float>(), dvalues.data_ptr<float>(),
+            partial.data_ptr<float>(), tick, loss.data_ptr<float>(), tk, stream());
+  TORCH_CHECK(err == hipSuccess, tiled ? "learner_head_fwd_tiled" : "learner_head_fwd",
+              " launch failed: ", hipGetErrorString(err));
   if (want_vs) return {loss, dlogits, dvalues, vs};
   return {loss, dlogits, dvalues};
+}
+
+std::vector<at::Tensor> learner_head_fwd(
+    at::Tensor core, at::Tensor wp, at::Tensor bp, at::Tensor wb, at::Tensor bb,
+    at::Tensor behaviour, at::Tensor actions, at::Tensor rewards, at::Tensor done,
+    at::Tensor ticket, double discounting, int64_t clip_mode, double clip_rho,
+    double clip_pg_rho, double baseline_cost, double entropy_cost,
+    c10::optional<at::Tensor> task, c10::optional<at::Tensor> mu,
+    c10::optional<at::Tensor> nu, bool want_vs) {
+  return head_fwd_impl(core, wp, bp, wb, bb, behaviour, actions, rewards, done, ticket,
+                       discounting, clip_mode, clip_rho, clip_pg_rho, baseline_cost,
+                       entropy_cost, task, mu, nu, want_vs, -1);
+}
+
+std::vector<at::Tensor> learner_head_fwd_tiled(
+    at::Tensor core, at::Tensor wp, at::Tensor bp, at::Tensor wb, at::Tensor bb,
+    at::Tensor behaviour, at::Tensor actions, at::Tensor rewards, at::Tensor done,
+    at::Tensor ticket, double discounting, int64_t clip_mode, double clip_rho,
+    double clip_pg_rho, double baseline_cost, double entropy_cost,
+    c10::optional<at::Tensor> task, c10::optional<at::Tensor> mu,
+    c10::optional<at::Tensor> nu, bool want_vs, int64_t time_tile) {
+  TORCH_CHECK(time_tile >= 0, "time_tile must be a multiple of 16 in [16, 1024], got ",
+              time_tile);
+  return head_fwd_impl(core, wp, bp, wb, bb, behaviour, actions, rewards, done, ticket,
+                       discounting, clip_mode, clip_rho, clip_pg_rho, baseline_cost,
+                       entropy_cost, task, mu, nu, want_vs, time_tile);
 }
 
 // -> dcore [T1,B,256]; the heads' gradients are ACCUMULATED into gwp/gbp/gwb/gbb
@@ -624,6 +679,19 @@ void register_learner_ops(pybind11::module& m) {
         pybind11::arg("baseline_cost"), pybind11::arg("entropy_cost"),
         pybind11::arg("task") = pybind11::none(), pybind11::arg("mu") = pybind11::none(),
         pybind11::arg("nu") = pybind11::none(), pybind11::arg("want_vs") = false);
+  m.def("learner_head_tile_auto", [](int64_t A) {
+    TORCH_CHECK(A >= 1 && A + 1 <= 64, "1 <= num_actions <= 63");
+    return (int64_t)sa::learner_head_tile_auto((int)A);
+  }, pybind11::arg("num_actions"));
+  m.def("learner_head_fwd_tiled", &learner_head_fwd_tiled, pybind11::arg("core"),
+        pybind11::arg("wp"), pybind11::arg("bp"), pybind11::arg("wb"), pybind11::arg("bb"),
+        pybind11::arg("behaviour"), pybind11::arg("actions"), pybind11::arg("rewards"),
+        pybind11::arg("done"), pybind11::arg("ticket"), pybind11::arg("discounting"),
+        pybind11::arg("clip_mode"), pybind11::arg("clip_rho"), pybind11::arg("clip_pg_rho"),
+        pybind11::arg("baseline_cost"), pybind11::arg("entropy_cost"),
+        pybind11::arg("task") = pybind11::none(), pybind11::arg("mu") = pybind11::none(),
+        pybind11::arg("nu") = pybind11::none(), pybind11::arg("want_vs") = false,
+        pybind11::arg("time_tile") = 0);
   m.def("learner_head_bwd", &learner_head_bwd, pybind11::arg("gscale"), pybind11::arg("core"),
         pybind11::arg("dlogits"), pybind11::arg("dvalues"), pybind11::arg("wp"),
         pybind11::arg("wb"), pybind11::arg("gwp"), pybind11::arg("gbp"), pybind11::arg("gwb"),

@@ -18,6 +18,7 @@ static staging slots; the data-parallel gradient sum is one RCCL all-reduce on
 the flat gradient buffer.
 """
 
+import logging
 import os
 import time
 
@@ -29,6 +30,18 @@ from .optim import FlatParams, RMSProp
 from .structs import ActorOutput, AgentOutput, StepOutput, StepOutputInfo
 from .utils.tracing import trace
 from .utils.knobs import measure_env
+
+
+_tiled_heads_logged = False
+
+
+def _log_tiled_heads_once(unroll, num_actions):
+  global _tiled_heads_logged
+  if not _tiled_heads_logged:
+    _tiled_heads_logged = True
+    logging.getLogger('rl').info(
+        'learner heads: time-tiled kernel (learner_head_fwd_tiled) for '
+        'unroll_length=%d, num_actions=%d', unroll, num_actions)
 
 
 def compute_loss(agent, data, flags, use_fused=False, popart=None,
@@ -44,13 +57,21 @@ def compute_loss(agent, data, flags, use_fused=False, popart=None,
   instr = env_outputs.observation[1]
   task_ids = data.level_name if popart is not None else None
   if (use_fused and agent.fused_core_ready(instr) and
-      agent.num_actions <= 31 and
+      agent.num_actions <= 63 and
       agent.num_actions + agent.num_value_heads <= 64 and
       (agent.num_value_heads == 1 or task_ids is not None)):
     # HIP learner path: fused core + fused heads/V-trace/loss; same math.
     # PopArt (multi-task heads, de-normalised V-trace, normalised baseline
     # error and advantages) runs inside the same kernels.
     from . import ops
+    # the whole-column head kernel where it fits (unroll within its LDS bound,
+    # at most 31 actions), the time-tiled one otherwise
+    unroll = env_outputs.reward.shape[0] - 1
+    time_tile = None
+    if (agent.num_actions > 31 or
+        unroll > ops.learner_head_max_unroll(agent.num_actions)):
+      time_tile = 'auto'
+      _log_tiled_heads_once(unroll, agent.num_actions)
     core_out, _ = agent.unroll_core(agent_outputs.action, env_outputs,
                                     data.agent_state)
     return ops.heads_vtrace_loss(
@@ -60,7 +81,7 @@ def compute_loss(agent, data, flags, use_fused=False, popart=None,
         reward_clipping=flags.reward_clipping,
         baseline_cost=flags.baseline_cost, entropy_cost=flags.entropy_cost,
         task_ids=task_ids, popart=popart,
-        aux=aux if popart is not None else None)
+        aux=aux if popart is not None else None, time_tile=time_tile)
   learner_outputs, _ = agent.unroll(agent_outputs.action, env_outputs,
                                     data.agent_state, sample=False,
                                     task_ids=task_ids)

@@ -16,6 +16,6 @@ from .conv_f32 import torso_forward_f32, linear_relu_f32  # noqa: F401
 from .core import core_lstm  # noqa: F401
 from .lang import language_lstm  # noqa: F401
 from .heads import heads_vtrace_loss, actor_heads_sample, PhiloxStream  # noqa: F401
-from .heads import learner_head_max_unroll  # noqa: F401
+from .heads import learner_head_max_unroll, learner_head_tile  # noqa: F401
 from .actor_core import actor_core_step, actor_core_pack  # noqa: F401
 from .grad_sink import direct_grads  # noqa: F401

@@ -9,6 +9,11 @@ the heads for all T+1 steps, V-trace, the loss sums and the analytic
 gradients w.r.t. the logits/values.  Backward: ONE kernel (learner_head_bwd)
 scales them by the incoming loss gradient, maps them through the heads
 (dcore) and accumulates the heads' weight/bias gradients (ops.grad_sink).
+learner_head_fwd keeps a whole batch column in LDS, which bounds the unroll
+(learner_head_max_unroll) and the action count (31).  Its time-tiled variant
+(learner_head_fwd_tiled, `time_tile`) walks the column in tiles of time_tile
+steps from the end of the unroll, carrying the V-trace accumulator between
+tiles: any unroll length, up to 63 actions, the same backward kernel.
 Multi-task PopArt (K value heads, per-column task index, de-normalised
 V-trace, normalised baseline error and scaled advantages) runs in the same
 two kernels; the PopArt statistics update stays a few device tensor ops
@@ -22,6 +27,8 @@ from ._ext import ext
 
 _CLIP = {'abs_one': 0, 'soft_asymmetric': 1}
 _TICKETS = {}
+# forward launches per head kernel (tests check which one a caller selected)
+head_kernel_calls = {'untiled': 0, 'tiled': 0}
 
 
 def _ticket(device):
@@ -36,8 +43,15 @@ def _ticket(device):
 def learner_head_max_unroll(num_actions):
   """Largest unroll length T the fused heads kernel takes at this action
   count: its per-column working set (dynamic and static LDS) has to fit one
-  workgroup.  heads_vtrace_loss raises RuntimeError above it."""
+  workgroup.  heads_vtrace_loss raises RuntimeError above it unless it is
+  given a time_tile.  num_actions <= 31."""
   return int(ext().learner_head_max_unroll(int(num_actions)))
+
+
+def learner_head_tile(num_actions):
+  """The default time tile (steps) of the time-tiled heads kernel at this
+  action count (num_actions <= 63): what time_tile='auto' selects."""
+  return int(ext().learner_head_tile_auto(int(num_actions)))
 
 
 class _HeadsVTraceLoss(torch.autograd.Function):
@@ -45,12 +59,19 @@ class _HeadsVTraceLoss(torch.autograd.Function):
   @staticmethod
   def forward(ctx, core, wp, bp, wb, bb, behaviour, actions, rewards, done,
               cfg, task, mu, nu, aux):
-    outs = ext().learner_head_fwd(
+    tile = cfg.get('time_tile')
+    kw = dict(task=task, mu=mu, nu=nu, want_vs=aux is not None)
+    if tile is None:
+      fwd = ext().learner_head_fwd
+    else:
+      fwd = ext().learner_head_fwd_tiled
+      kw['time_tile'] = tile
+    outs = fwd(
         core, wp, bp, wb.reshape(-1), bb.reshape(-1), behaviour, actions,
         rewards, done, _ticket(core.device), cfg['discounting'],
         _CLIP[cfg['reward_clipping']], 1.0, 1.0, cfg['baseline_cost'],
-        cfg['entropy_cost'], task=task, mu=mu, nu=nu,
-        want_vs=aux is not None)
+        cfg['entropy_cost'], **kw)
+    head_kernel_calls['untiled' if tile is None else 'tiled'] += 1
     loss, dl, dv = outs[:3]
     if aux is not None:
       aux['targets'] = outs[3]
@@ -73,7 +94,7 @@ class _HeadsVTraceLoss(torch.autograd.Function):
 def heads_vtrace_loss(core_out, policy_w, policy_b, baseline_w, baseline_b,
                       behaviour_logits, actions, rewards, done, discounting,
                       reward_clipping, baseline_cost, entropy_cost,
-                      task_ids=None, popart=None, aux=None):
+                      task_ids=None, popart=None, aux=None, time_tile=None):
   """core_out [T+1,B,256] f32 from the learner unroll; behaviour_logits /
   actions / rewards / done: the FULL [T+1,B,...] batch tensors (rows 1..T
   are used, as in experiment.py:360-375).  Returns the total loss (sum).
@@ -81,10 +102,21 @@ def heads_vtrace_loss(core_out, policy_w, policy_b, baseline_w, baseline_b,
   Multi-task value heads: baseline_w [256, K], baseline_b [K] and task_ids
   [B] (the head of each batch column).  popart: a PopArt whose mu / nu
   de-normalise the values inside the kernel (popart.py); aux: a dict that
-  receives 'targets' = the V-trace targets vs [T, B] for its update."""
+  receives 'targets' = the V-trace targets vs [T, B] for its update.
+
+  time_tile: None runs learner_head_fwd (T <= learner_head_max_unroll(A),
+  A <= 31; RuntimeError 'unroll too long' above the limit).  An int (a
+  multiple of 16 in [16, 1024] whose working set fits the LDS) or 'auto'
+  (learner_head_tile(A)) runs the time-tiled kernel: any T, A <= 63."""
   cfg = dict(discounting=float(discounting), reward_clipping=reward_clipping,
              baseline_cost=float(baseline_cost),
              entropy_cost=float(entropy_cost))
+  if time_tile is not None:
+    if isinstance(time_tile, str):
+      if time_tile != 'auto':
+        raise ValueError("time_tile: None, an int or 'auto', got %r" % time_tile)
+      time_tile = learner_head_tile(policy_w.shape[1])
+    cfg['time_tile'] = int(time_tile)
   task = None if task_ids is None else task_ids.to(torch.int64).contiguous()
   mu = nu = None
   if popart is not None:
