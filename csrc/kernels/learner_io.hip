@@ -21,6 +21,8 @@
 //                      accumulator carried between them: LDS bounded by the
 //                      tile, so any unroll length and up to 63 actions (a
 //                      64-column W image); same ticket, same outputs.
+//                      The phases and the LDS layouts of both kernels are
+//                      defined, and described, once in head_core.h.
 //  * learner_head_bwd  dcore = g (dlogits W_p^T + dv W_b[:, task]^T) and the
 //                      heads' weight/bias gradients (per-row-chunk slots
 //                      summed in a fixed order), g = the incoming loss
@@ -33,6 +35,7 @@
 //  * relu_bwd_colsum   dY *= (Y > 0) in place on bf16 + column sums (torso FC
 //                      ReLU + bias gradient).
 //  * relu_mask_bf16    dX *= (X > 0) in place (the torso's final ReLU).
+#include "head_core.h"
 #include "launchers.h"
 
 #include <hip/hip_bf16.h>
@@ -41,7 +44,6 @@ namespace sa {
 namespace {
 
 typedef unsigned short bf16_t;  // raw bf16 bits
-typedef float f4v __attribute__((ext_vector_type(4)));
 
 __device__ __forceinline__ float bf2f(bf16_t v) {
   return __uint_as_float(static_cast<unsigned>(v) << 16);
@@ -50,18 +52,6 @@ __device__ __forceinline__ bf16_t f2bf(float f) {  // round to nearest even
   unsigned u = __float_as_uint(f);
   u += 0x7fffu + ((u >> 16) & 1u);
   return static_cast<bf16_t>(u >> 16);
-}
-
-__device__ __forceinline__ float clip_reward(float r, int mode) {
-  if (mode == 0) return fminf(fmaxf(r, -1.f), 1.f);       // abs_one
-  const float sq = tanhf(r / 5.0f);                         // soft_asymmetric
-  return (r < 0.f ? 0.3f * sq : sq) * 5.0f;
-}
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
 }
 
 // Phase timestamps of block 0 for tools/micro/head_trace.hip (compiled out).
@@ -75,32 +65,24 @@ namespace {
 #define HEAD_TRACE(i)
 #endif
 
-constexpr int kHeadThreads = 1024;
-// PopArt sigma bounds (popart.py SIGMA_MIN / SIGMA_MAX)
-constexpr float kPopArtSigmaMin = 1e-4f;
-constexpr float kPopArtSigmaMax = 1e6f;
-constexpr int kHeadWaves = kHeadThreads / 64;
 constexpr int kMaxA = 31;      // A + 1 head outputs <= 32
-// LDS of one workgroup: learner_head_fwd's dynamic arrays and its static ones
-// (scan_a, scan_b, red, last_s; kHeadStaticLds bounds them, asserted next to
-// their declarations) must fit together
+// LDS of one workgroup: a head kernel's dynamic arrays (HeadLds /
+// HeadTiledLds) and its static ones (scan_a, scan_b, red, last_s, carry_s;
+// kHeadStaticLds bounds them, asserted next to their declarations) must fit
+// together
 constexpr size_t kLdsPerWorkgroup = 160 * 1024;
 constexpr size_t kHeadStaticLds =
     sizeof(float) * (2 * kHeadThreads + 3 * kHeadWaves) + 16;
 
 // ------------------------------------------------------------ heads + V-trace
-// core [T1,B,H] (H == 256), Wp [H,A], Wb [H] (one value head).  The V-trace
-// inputs are the learner's time-shifted views (compute_loss): target logits
-// / values = heads at t < T, bootstrap = value at T, behaviour logits,
-// actions, rewards, done = rows 1..T of the batch (the caller passes
-// pointers to row 1).  Every global operand of the column is fetched in the
-// prologue with all loads in flight (one memory round trip), then the
-// phases run out of LDS.  The heads are fp32 MFMA (16x16x4): wave w owns
-// rows [16w, 16w+16) of the column, lane l sums k in [64(l>>4), +64), so its
-// A operand is 64 contiguous floats of one core row.  LDS (dynamic, 4-byte
-// words): W [H][MAXC] (zero-padded) | logits/values [T1][A+1] | behaviour
-// [T][A] | a_t, delta_t, pgrho_t [T] | vs_t [T+1] | reward [T] | action [T]
-// | done [T].
+// core [T1,B,H] (H == 256), Wp [H,A], Wb [H,K].  The V-trace inputs are the
+// learner's time-shifted views (compute_loss): target logits / values = heads
+// at t < T, bootstrap = value at T, behaviour logits, actions, rewards, done =
+// rows 1..T of the batch (the caller passes pointers to row 1).  Every global
+// operand of the column is fetched in the prologue with all loads in flight
+// (one memory round trip), then the phases of head_core.h run out of LDS
+// (HeadLds).  Wave w owns head rows [16w, 16w+16); a thread scans a chunk of
+// ceil(T / 1024) steps.
 template <int MAXC>
 __global__ __launch_bounds__(kHeadThreads) void learner_head_fwd_kernel(
     const float* __restrict__ core, const float* __restrict__ wp,
@@ -112,20 +94,22 @@ __global__ __launch_bounds__(kHeadThreads) void learner_head_fwd_kernel(
     float entropy_cost, float* __restrict__ dlogits, float* __restrict__ dvalues,
     float* __restrict__ partial, unsigned* __restrict__ ticket,
     float* __restrict__ loss, HeadTasks tk) {
-  constexpr int H = 256;
+  using Image = HeadImage<MAXC>;
+  constexpr int H = Image::H;
   extern __shared__ float smem[];
   const int A1 = A + 1;
   const int T1 = T + 1;
-  float* w_s = smem;                 // [H][MAXC] + 4 x 16 pad
-  float* lv_s = w_s + H * MAXC + 64; // [T1][A1]: logits then value
-  float* beh_s = lv_s + T1 * A1;     // [T][A]
-  float* a_s = beh_s + T * A;        // gamma_t c_t
-  float* d_s = a_s + T;              // delta_t
-  float* p_s = d_s + T;              // clipped pg rho
-  float* vs_s = p_s + T;             // vs_t, vs_s[T] = bootstrap
-  float* r_s = vs_s + T + 1;         // clipped reward
-  int* act_s = reinterpret_cast<int*>(r_s + T);
-  float* disc_s = reinterpret_cast<float*>(act_s + T);
+  const HeadLds L(MAXC, T, A);
+  float* w_s = smem + L.w;
+  float* lv_s = smem + L.lv;
+  float* beh_s = smem + L.beh;
+  float* a_s = smem + L.a;
+  float* d_s = smem + L.d;
+  float* p_s = smem + L.p;
+  float* vs_s = smem + L.vs;
+  float* r_s = smem + L.r;
+  int* act_s = reinterpret_cast<int*>(smem + L.act);
+  float* disc_s = smem + L.disc;
   __shared__ float scan_a[kHeadThreads], scan_b[kHeadThreads];
   __shared__ float red[3][kHeadWaves];
   __shared__ bool last_s;
@@ -137,25 +121,11 @@ __global__ __launch_bounds__(kHeadThreads) void learner_head_fwd_kernel(
   const int tid = threadIdx.x;
   const int lane = tid & 63;
   const int wave = tid >> 6;
-  // this column's value head and its PopArt statistics (identity without)
-  // a task id outside [0, K) reads head 0 (no out-of-bounds access) with a
-  // NaN sigma: the column's gradients turn NaN and the RMSProp step guard
-  // drops the update (counted in skipped_updates) instead of training on it
-  const int64_t kt_raw = tk.task != nullptr ? tk.task[b] : 0;
-  const bool kt_bad = kt_raw < 0 || kt_raw >= tk.K;
-  const int kt = kt_bad ? 0 : static_cast<int>(kt_raw);
-  float sig = 1.f, mu = 0.f;
-  if (tk.mu != nullptr) {
-    mu = tk.mu[kt];
-    const float var = fmaxf(tk.nu[kt] - mu * mu, kPopArtSigmaMin * kPopArtSigmaMin);
-    sig = fminf(fmaxf(sqrtf(var), kPopArtSigmaMin), kPopArtSigmaMax);
-  }
-  if (kt_bad) sig = __builtin_nanf("");
-  const float rsig = 1.f / sig;
+  const ColumnStats cs = column_stats(tk, b);
+  const float sig = cs.sig, mu = cs.mu;
 
   HEAD_TRACE(0);
   // ---- prologue: every load of the column issued before any is consumed
-  constexpr int NCT = MAXC / 16;  // 16-wide output column tiles
   const int ntiles = (T1 + 15) / 16;
   const int arow = lane & 15, kq = lane >> 4;
   float4 xa[16];  // A operand: core[16 tile + arow][64 kq + 4j .. +3]
@@ -167,21 +137,9 @@ __global__ __launch_bounds__(kHeadThreads) void learner_head_fwd_kernel(
     for (int j = 0; j < 16; ++j) xa[j] = t < T1 ? src[j] : float4{0.f, 0.f, 0.f, 0.f};
   };
   if (wave < ntiles) load_a(wave);
-  float bias[NCT];
-#pragma unroll
-  for (int ct = 0; ct < NCT; ++ct) {
-    const int c = 16 * ct + arow;
-    bias[ct] = c < A ? bp[c] : (c == A ? bb[kt] : 0.f);
-  }
   // (register-staged: every load below is issued before the first LDS store)
-  constexpr int WPT = H * MAXC / kHeadThreads;
-  float wv[WPT];
-#pragma unroll
-  for (int j = 0; j < WPT; ++j) {
-    const int i = tid + j * kHeadThreads;
-    const int k = i / MAXC, c = i - k * MAXC;
-    wv[j] = c < A ? wp[k * A + c] : (c == A ? wb[k * tk.K + kt] : 0.f);
-  }
+  float bias[Image::NCT], wv[Image::WPT];
+  Image::load(wv, bias, wp, wb, bp, bb, A, tk.K, cs.kt);
   constexpr int BPT = 2;  // behaviour logits per thread staged in registers
   float bv[BPT];
 #pragma unroll
@@ -198,13 +156,7 @@ __global__ __launch_bounds__(kHeadThreads) void learner_head_fwd_kernel(
     av = static_cast<int>(actions[idx]);
     dn = done[idx] ? 0.f : discounting;
   }
-  // W (k, c) at k MAXC + 16 (k / 64) + c: the 4 k-quarters of a wave's B
-  // operand reads land 16 banks apart
-#pragma unroll
-  for (int j = 0; j < WPT; ++j) {
-    const int i = tid + j * kHeadThreads;
-    w_s[i + 16 * ((i / MAXC) >> 6)] = wv[j];
-  }
+  Image::store(w_s, wv);
 #pragma unroll
   for (int j = 0; j < BPT; ++j) {
     const int i = tid + j * kHeadThreads;
@@ -228,68 +180,33 @@ __global__ __launch_bounds__(kHeadThreads) void learner_head_fwd_kernel(
   __syncthreads();
   HEAD_TRACE(1);
 
-  // ---- heads: [16 rows x 256] x [256 x 16 cols] per wave on fp32 MFMA
+  // ---- heads of rows 0 .. T
   for (int tile = wave; tile < ntiles; tile += kHeadWaves) {
     if (tile != wave) load_a(tile);
-    f4v acc[NCT];
-#pragma unroll
-    for (int ct = 0; ct < NCT; ++ct) acc[ct] = f4v{0.f, 0.f, 0.f, 0.f};
+    f4v acc[Image::NCT];
+    Image::zero(acc);
     const float* wk = w_s + (64 * kq) * MAXC + 16 * kq + arow;
 #pragma unroll
-    for (int j = 0; j < 16; ++j) {
-      const float av[4] = {xa[j].x, xa[j].y, xa[j].z, xa[j].w};
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-#pragma unroll
-        for (int ct = 0; ct < NCT; ++ct)
-          acc[ct] = __builtin_amdgcn_mfma_f32_16x16x4f32(
-              av[q], wk[(4 * j + q) * MAXC + 16 * ct], acc[ct], 0, 0, 0);
-      }
-    }
-    // D[row 4 kq + i][col arow]
-#pragma unroll
-    for (int ct = 0; ct < NCT; ++ct) {
-      const int c = 16 * ct + arow;
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const int t = 16 * tile + 4 * kq + i;
-        if (t < T1 && c < A1) lv_s[t * A1 + c] = acc[ct][i] + bias[ct];
-      }
-    }
+    for (int j = 0; j < 16; ++j) Image::mac4(acc, xa[j], wk + 4 * j * MAXC);
+    Image::write(lv_s, acc, bias, 16 * tile, T1, A1);
   }
   __syncthreads();
   HEAD_TRACE(2);
 
-  // ---- V-trace elementwise (vtrace.py:143-147, 235-262)
+  // ---- V-trace step terms, on the de-normalised (PopArt) values
   for (int t = tid; t < T; t += kHeadThreads) {
     const float* zt = lv_s + t * A1;
-    const float* zb = beh_s + t * A;
-    const int a = act_s[t];
-    float mt = -INFINITY, mb = -INFINITY;
-    for (int j = 0; j < A; ++j) {
-      mt = fmaxf(mt, zt[j]);
-      mb = fmaxf(mb, zb[j]);
-    }
-    float st = 0.f, sb = 0.f;
-    for (int j = 0; j < A; ++j) {
-      st += __expf(zt[j] - mt);
-      sb += __expf(zb[j] - mb);
-    }
-    const float log_pi = zt[a] - mt - __logf(st);
-    const float log_mu = zb[a] - mb - __logf(sb);
-    const float rho = __expf(log_pi - log_mu);
-    const float disc = disc_s[t];
-    const float v = sig * zt[A] + mu;  // de-normalised (PopArt) values
-    const float v1 = sig * lv_s[(t + 1) * A1 + A] + mu;
-    a_s[t] = disc * fminf(1.0f, rho);
-    d_s[t] = fminf(clip_rho, rho) * (r_s[t] + disc * v1 - v);
-    p_s[t] = fminf(clip_pg_rho, rho);
+    const VtraceStep s = vtrace_step(zt, beh_s + t * A, A, act_s[t], r_s[t], disc_s[t],
+                                     sig * zt[A] + mu, sig * lv_s[(t + 1) * A1 + A] + mu,
+                                     clip_rho, clip_pg_rho);
+    a_s[t] = s.a;
+    d_s[t] = s.delta;
+    p_s[t] = s.pg_rho;
   }
   __syncthreads();
   HEAD_TRACE(3);
 
-  // ---- reverse recursion acc_t = delta_t + a_t acc_{t+1}: each thread
-  // composes a chunk of C steps, then a workgroup suffix scan of the maps
+  // ---- reverse recursion: per-thread chunks, then the workgroup suffix scan
   const int C = (T + kHeadThreads - 1) / kHeadThreads;
   const int t0 = tid * C;
   const int t1 = min(t0 + C, T);
@@ -298,24 +215,12 @@ __global__ __launch_bounds__(kHeadThreads) void learner_head_fwd_kernel(
     cb = d_s[t] + a_s[t] * cb;
     ca = a_s[t] * ca;
   }
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {  // wave-level inclusive suffix
-    const float na = __shfl_down(ca, d, 64);
-    const float nb = __shfl_down(cb, d, 64);
-    if (lane + d < 64) {
-      cb = cb + ca * nb;
-      ca = ca * na;
-    }
-  }
+  wave_affine_suffix(ca, cb, lane);
   scan_a[tid] = ca;
   scan_b[tid] = cb;
   __syncthreads();
   HEAD_TRACE(4);
-  // acc entering this thread's chunk from the right: the later waves'
-  // totals, then the next lane's inclusive suffix in this wave
-  float acc = 0.f;
-  for (int w = kHeadWaves - 1; w > wave; --w) acc = scan_b[w * 64] + scan_a[w * 64] * acc;
-  if (lane < 63) acc = scan_b[tid + 1] + scan_a[tid + 1] * acc;
+  float acc = enter_from_right(scan_a, scan_b, 0.f);
   for (int t = t1 - 1; t >= t0; --t) {
     acc = d_s[t] + a_s[t] * acc;
     vs_s[t] = acc + (sig * lv_s[t * A1 + A] + mu);
@@ -325,104 +230,37 @@ __global__ __launch_bounds__(kHeadThreads) void learner_head_fwd_kernel(
   HEAD_TRACE(5);
 
   // ---- advantages, loss terms and their gradients
-  float l_pg = 0.f, l_bl = 0.f, l_ent = 0.f;
+  LossSums l;
   for (int t = tid; t < T; t += kHeadThreads) {
-    const int64_t idx = static_cast<int64_t>(t) * B + b;
     const float* zt = lv_s + t * A1;
-    float* dz = dlogits + idx * A;
-    const int a = act_s[t];
     const float n = zt[A];
-    const float v = sig * n + mu;
-    const float vs = vs_s[t];
-    // PopArt: advantages in normalised units, baseline error against the
-    // normalised target (sig = 1, mu = 0: the plain IMPALA loss, bitwise)
-    const float pg_adv = p_s[t] * (r_s[t] + disc_s[t] * vs_s[t + 1] - v) * rsig;
-    const float err = (vs - mu) * rsig - n;
-    if (tk.vs_out != nullptr) tk.vs_out[idx] = vs;
-    float m = -INFINITY;
-    for (int j = 0; j < A; ++j) m = fmaxf(m, zt[j]);
-    float s = 0.f;
-    for (int j = 0; j < A; ++j) s += __expf(zt[j] - m);
-    const float lse = m + __logf(s);
-    float Hn = 0.f;
-    for (int j = 0; j < A; ++j) {
-      const float lp = zt[j] - lse;
-      Hn -= __expf(lp) * lp;
-    }
-    for (int j = 0; j < A; ++j) {
-      const float lp = zt[j] - lse;
-      const float p = __expf(lp);
-      dz[j] = (p - (j == a ? 1.f : 0.f)) * pg_adv + entropy_cost * p * (lp + Hn);
-    }
-    dvalues[idx] = -baseline_cost * err;
-    l_pg += (lse - zt[a]) * pg_adv;
-    l_bl += 0.5f * err * err;
-    l_ent -= Hn;
+    loss_step<true>(zt, A, act_s[t], n, sig * n + mu, vs_s[t], vs_s[t + 1], p_s[t],
+                    r_s[t], disc_s[t], mu, cs.rsig, baseline_cost, entropy_cost,
+                    static_cast<int64_t>(t) * B + b, dlogits, dvalues, tk.vs_out, nullptr,
+                    l);
   }
-  l_pg = wave_sum(l_pg);
-  l_bl = wave_sum(l_bl);
-  l_ent = wave_sum(l_ent);
-  if (lane == 0) {
-    red[0][wave] = l_pg;
-    red[1][wave] = l_bl;
-    red[2][wave] = l_ent;
-  }
-  __syncthreads();
+  reduce_to_waves(l, red);
   HEAD_TRACE(6);
-  if (tid == 0) {
-    float pg = 0.f, bl = 0.f, en = 0.f;
-    for (int w = 0; w < kHeadWaves; ++w) {
-      pg += red[0][w];
-      bl += red[1][w];
-      en += red[2][w];
-    }
-    // publish the partials write-through (sc1), wait for them, then take a
-    // ticket; the last block reads them with sc1 loads after its add
-    // returned - no L2 write-back / invalidate fences (MI355X_MICROARCH.md,
-    // inter-workgroup visibility, the one-lane sc1 hand-off)
-    __hip_atomic_store(partial + b * 3 + 0, pg, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __hip_atomic_store(partial + b * 3 + 1, bl, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __hip_atomic_store(partial + b * 3 + 2, en, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    const unsigned prev = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED,
-                                                 __HIP_MEMORY_SCOPE_AGENT);
-    last_s = (prev == static_cast<unsigned>(gridDim.x) - 1);
-  }
+  if (tid == 0) last_s = publish_column(partial, ticket, b, sum_waves(red));
   __syncthreads();
   HEAD_TRACE(7);
-  if (last_s && tid == 0) {
-    float pg = 0.f, bl = 0.f, en = 0.f;
-    for (int j = 0; j < B; ++j) {  // fixed order: deterministic
-      pg += __hip_atomic_load(partial + j * 3 + 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      bl += __hip_atomic_load(partial + j * 3 + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      en += __hip_atomic_load(partial + j * 3 + 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    loss[1] = pg;
-    loss[2] = bl;
-    loss[3] = en;
-    loss[0] = pg + baseline_cost * bl + entropy_cost * en;
-    __hip_atomic_store(ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // next launch
-  }
+  if (last_s && tid == 0) total_loss(partial, ticket, B, baseline_cost, entropy_cost, loss);
   HEAD_TRACE(8);
 }
 
 // -------------------------------------------------- heads + V-trace, time-tiled
 // The same column computation with LDS bounded by a time tile of TC steps
-// instead of by T, for unrolls past learner_head_fwd_max_unroll and for
-// A + 1 up to 64 head columns.  The V-trace recursion runs backward in time
-// with a scalar carry, so the column is walked in tiles [c0, c1) of TC steps
-// from the END of the unroll (the tile at t = 0 takes the remainder).  Per
-// tile: heads of rows c0 .. c1 (row c1 gives v_{t+1} of the tile's last step:
-// the bootstrap row T in the first tile, recomputed otherwise), the V-trace
-// terms, the reverse scan seeded with the carried acc_{c1}, then vs, the
-// advantages (vs_{c1} carried; the bootstrap value in the first tile), the
-// loss terms and gradients.  acc_{c0} / vs_{c0} go to the next tile through
-// carry_s.  TC <= kHeadThreads: one step per thread and tile.  The loss
-// partial sums stay in registers over all tiles and are reduced once.  Every
-// barrier is reached by all threads in every tile.  LDS (dynamic, 4-byte
-// words): W [H][MAXC] + 64 | logits/values [TC+1][A+1] | behaviour [TC][A] |
-// a_t, delta_t, pgrho_t, reward, action, discount [TC] | vs_t [TC+1] (2 TC
-// words reserved).
+// instead of by T (HeadTiledLds), for unrolls past learner_head_fwd_max_unroll
+// and for A + 1 up to 64 head columns.  The V-trace recursion runs backward in
+// time with a scalar carry, so the column is walked in tiles [c0, c1) of TC
+// steps from the END of the unroll (the tile at t = 0 takes the remainder).
+// Per tile the phases run on rows c0 .. c1: row c1 gives v_{t+1} of the tile's
+// last step (the bootstrap row T in the first tile, recomputed otherwise), the
+// scan is entered with the carried acc_{c1}, and vs_{c1} is the carried one
+// (the bootstrap value in the first tile).  acc_{c0} / vs_{c0} go to the next
+// tile through carry_s.  TC <= kHeadThreads: one step per thread and tile.
+// The loss sums stay in registers over all tiles and are reduced once.  Every
+// barrier is reached by all threads in every tile.
 template <int MAXC>
 __global__ __launch_bounds__(kHeadThreads) void learner_head_fwd_tiled_kernel(
     const float* __restrict__ core, const float* __restrict__ wp,
@@ -434,19 +272,21 @@ __global__ __launch_bounds__(kHeadThreads) void learner_head_fwd_tiled_kernel(
     float entropy_cost, float* __restrict__ dlogits, float* __restrict__ dvalues,
     float* __restrict__ partial, unsigned* __restrict__ ticket,
     float* __restrict__ loss, HeadTasks tk, int TC) {
-  constexpr int H = 256;
+  using Image = HeadImage<MAXC>;
+  constexpr int H = Image::H;
   extern __shared__ float smem[];
   const int A1 = A + 1;
-  float* w_s = smem;                      // [H][MAXC] + 4 x 16 pad
-  float* lv_s = w_s + H * MAXC + 64;      // [TC+1][A1]: logits then value
-  float* beh_s = lv_s + (TC + 1) * A1;    // [TC][A]
-  float* a_s = beh_s + TC * A;            // gamma_t c_t
-  float* d_s = a_s + TC;                  // delta_t
-  float* p_s = d_s + TC;                  // clipped pg rho
-  float* r_s = p_s + TC;                  // clipped reward
-  int* act_s = reinterpret_cast<int*>(r_s + TC);
-  float* disc_s = reinterpret_cast<float*>(act_s + TC);
-  float* vs_s = disc_s + TC;              // vs_t, vs_s[n] = vs_{c1}
+  const HeadTiledLds L(MAXC, TC, A);
+  float* w_s = smem + L.w;
+  float* lv_s = smem + L.lv;
+  float* beh_s = smem + L.beh;
+  float* a_s = smem + L.a;
+  float* d_s = smem + L.d;
+  float* p_s = smem + L.p;
+  float* r_s = smem + L.r;
+  int* act_s = reinterpret_cast<int*>(smem + L.act);
+  float* disc_s = smem + L.disc;
+  float* vs_s = smem + L.vs;
   __shared__ float scan_a[kHeadThreads], scan_b[kHeadThreads];
   __shared__ float red[3][kHeadWaves];
   __shared__ float carry_s[2];            // acc_{c0}, vs_{c0} of the last tile
@@ -458,48 +298,20 @@ __global__ __launch_bounds__(kHeadThreads) void learner_head_fwd_tiled_kernel(
   const int tid = threadIdx.x;
   const int lane = tid & 63;
   const int wave = tid >> 6;
-  // value head and PopArt statistics of the column, as learner_head_fwd (a
-  // bad task id: head 0 with a NaN sigma)
-  const int64_t kt_raw = tk.task != nullptr ? tk.task[b] : 0;
-  const bool kt_bad = kt_raw < 0 || kt_raw >= tk.K;
-  const int kt = kt_bad ? 0 : static_cast<int>(kt_raw);
-  float sig = 1.f, mu = 0.f;
-  if (tk.mu != nullptr) {
-    mu = tk.mu[kt];
-    const float var = fmaxf(tk.nu[kt] - mu * mu, kPopArtSigmaMin * kPopArtSigmaMin);
-    sig = fminf(fmaxf(sqrtf(var), kPopArtSigmaMin), kPopArtSigmaMax);
-  }
-  if (kt_bad) sig = __builtin_nanf("");
-  const float rsig = 1.f / sig;
+  const ColumnStats cs = column_stats(tk, b);
+  const float sig = cs.sig, mu = cs.mu;
 
-  // ---- W image, once per column (the layout of learner_head_fwd)
-  constexpr int NCT = MAXC / 16;  // 16-wide output column tiles
+  // ---- W image, once per column
   const int arow = lane & 15, kq = lane >> 4;
-  float bias[NCT];
-#pragma unroll
-  for (int ct = 0; ct < NCT; ++ct) {
-    const int c = 16 * ct + arow;
-    bias[ct] = c < A ? bp[c] : (c == A ? bb[kt] : 0.f);
-  }
-  constexpr int WPT = H * MAXC / kHeadThreads;
-  float wv[WPT];
-#pragma unroll
-  for (int j = 0; j < WPT; ++j) {
-    const int i = tid + j * kHeadThreads;
-    const int k = i / MAXC, c = i - k * MAXC;
-    wv[j] = c < A ? wp[k * A + c] : (c == A ? wb[k * tk.K + kt] : 0.f);
-  }
-#pragma unroll
-  for (int j = 0; j < WPT; ++j) {
-    const int i = tid + j * kHeadThreads;
-    w_s[i + 16 * ((i / MAXC) >> 6)] = wv[j];
-  }
+  float bias[Image::NCT], wv[Image::WPT];
+  Image::load(wv, bias, wp, wb, bp, bb, A, tk.K, cs.kt);
+  Image::store(w_s, wv);
   if (tid == 0) {
     carry_s[0] = 0.f;  // acc_T
     carry_s[1] = 0.f;  // (the first tile takes the bootstrap value instead)
   }
 
-  float l_pg = 0.f, l_bl = 0.f, l_ent = 0.f;
+  LossSums l;
   const int ntt = (T + TC - 1) / TC;
   for (int tt = 0; tt < ntt; ++tt) {
     const int c1 = T - tt * TC;
@@ -533,87 +345,43 @@ __global__ __launch_bounds__(kHeadThreads) void learner_head_fwd_tiled_kernel(
       disc_s[tid] = done[idx] ? 0.f : discounting;
     }
 
-    // ---- heads of rows c0 .. c1: [16 rows x 256] x [256 x 16 cols] per wave
+    // ---- heads of rows c0 .. c1
     for (int tile = wave; tile < nrt; tile += kHeadWaves) {
-      f4v acc[NCT];
-#pragma unroll
-      for (int ct = 0; ct < NCT; ++ct) acc[ct] = f4v{0.f, 0.f, 0.f, 0.f};
+      f4v acc[Image::NCT];
+      Image::zero(acc);
 #pragma unroll 1
       for (int h = 0; h < 2; ++h) {
         if (tile != wave || h != 0) load_a(tile, h);
         const float* wk = w_s + (64 * kq + 32 * h) * MAXC + 16 * kq + arow;
 #pragma unroll
-        for (int j = 0; j < 8; ++j) {
-          const float av[4] = {xa[j].x, xa[j].y, xa[j].z, xa[j].w};
-#pragma unroll
-          for (int q = 0; q < 4; ++q) {
-#pragma unroll
-            for (int ct = 0; ct < NCT; ++ct)
-              acc[ct] = __builtin_amdgcn_mfma_f32_16x16x4f32(
-                  av[q], wk[(4 * j + q) * MAXC + 16 * ct], acc[ct], 0, 0, 0);
-          }
-        }
+        for (int j = 0; j < 8; ++j) Image::mac4(acc, xa[j], wk + 4 * j * MAXC);
       }
-      // D[row 4 kq + i][col arow]
-#pragma unroll
-      for (int ct = 0; ct < NCT; ++ct) {
-        const int c = 16 * ct + arow;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          const int row = 16 * tile + 4 * kq + i;
-          if (row <= n && c < A1) lv_s[row * A1 + c] = acc[ct][i] + bias[ct];
-        }
-      }
+      Image::write(lv_s, acc, bias, 16 * tile, n + 1, A1);
     }
     __syncthreads();
 
-    // ---- V-trace elementwise (vtrace.py:143-147, 235-262)
+    // ---- V-trace step terms, on the de-normalised (PopArt) values
     if (on) {
       const float* zt = lv_s + tid * A1;
-      const float* zb = beh_s + tid * A;
-      const int a = act_s[tid];
-      float mt = -INFINITY, mb = -INFINITY;
-      for (int j = 0; j < A; ++j) {
-        mt = fmaxf(mt, zt[j]);
-        mb = fmaxf(mb, zb[j]);
-      }
-      float st = 0.f, sb = 0.f;
-      for (int j = 0; j < A; ++j) {
-        st += __expf(zt[j] - mt);
-        sb += __expf(zb[j] - mb);
-      }
-      const float log_pi = zt[a] - mt - __logf(st);
-      const float log_mu = zb[a] - mb - __logf(sb);
-      const float rho = __expf(log_pi - log_mu);
-      const float disc = disc_s[tid];
-      const float v = sig * zt[A] + mu;  // de-normalised (PopArt) values
-      const float v1 = sig * lv_s[(tid + 1) * A1 + A] + mu;
-      a_s[tid] = disc * fminf(1.0f, rho);
-      d_s[tid] = fminf(clip_rho, rho) * (r_s[tid] + disc * v1 - v);
-      p_s[tid] = fminf(clip_pg_rho, rho);
+      const VtraceStep s = vtrace_step(zt, beh_s + tid * A, A, act_s[tid], r_s[tid],
+                                       disc_s[tid], sig * zt[A] + mu,
+                                       sig * lv_s[(tid + 1) * A1 + A] + mu, clip_rho,
+                                       clip_pg_rho);
+      a_s[tid] = s.a;
+      d_s[tid] = s.delta;
+      p_s[tid] = s.pg_rho;
     }
     __syncthreads();
 
-    // ---- reverse recursion acc_t = delta_t + a_t acc_{t+1} over the tile:
-    // a workgroup suffix scan of the per-step maps (identity past the tile's
-    // end), entered from the right with the carried acc_{c1}
+    // ---- reverse recursion over the tile: the workgroup suffix scan of the
+    // per-step maps (identity past the tile's end), entered with acc_{c1}
     float ca = on ? a_s[tid] : 1.f;  // acc_t = cb + ca * acc_{t+1}
     float cb = on ? d_s[tid] : 0.f;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {  // wave-level inclusive suffix
-      const float na = __shfl_down(ca, d, 64);
-      const float nb = __shfl_down(cb, d, 64);
-      if (lane + d < 64) {
-        cb = cb + ca * nb;
-        ca = ca * na;
-      }
-    }
+    wave_affine_suffix(ca, cb, lane);
     scan_a[tid] = ca;
     scan_b[tid] = cb;
     __syncthreads();
-    float acc = acc_in;
-    for (int w = kHeadWaves - 1; w > wave; --w) acc = scan_b[w * 64] + scan_a[w * 64] * acc;
-    if (lane < 63) acc = scan_b[tid + 1] + scan_a[tid + 1] * acc;
+    float acc = enter_from_right(scan_a, scan_b, acc_in);
     if (on) {
       acc = d_s[tid] + a_s[tid] * acc;
       const float vs = acc + (sig * lv_s[tid * A1 + A] + mu);
@@ -628,80 +396,20 @@ __global__ __launch_bounds__(kHeadThreads) void learner_head_fwd_tiled_kernel(
 
     // ---- advantages, loss terms and their gradients
     if (on) {
-      const int64_t idx = static_cast<int64_t>(c0 + tid) * B + b;
       const float* zt = lv_s + tid * A1;
-      float* dz = dlogits + idx * A;
-      const int a = act_s[tid];
       const float nv = zt[A];
-      const float v = sig * nv + mu;
-      const float vs = vs_s[tid];
-      // PopArt: advantages in normalised units, baseline error against the
-      // normalised target (sig = 1, mu = 0: the plain IMPALA loss)
-      const float pg_adv = p_s[tid] * (r_s[tid] + disc_s[tid] * vs_s[tid + 1] - v) * rsig;
-      const float err = (vs - mu) * rsig - nv;
-      if (tk.vs_out != nullptr) tk.vs_out[idx] = vs;
-      float m = -INFINITY;
-      for (int j = 0; j < A; ++j) m = fmaxf(m, zt[j]);
-      float s = 0.f;
-      for (int j = 0; j < A; ++j) s += __expf(zt[j] - m);
-      const float lse = m + __logf(s);
-      float Hn = 0.f;
-      for (int j = 0; j < A; ++j) {
-        const float lp = zt[j] - lse;
-        Hn -= __expf(lp) * lp;
-      }
-      for (int j = 0; j < A; ++j) {
-        const float lp = zt[j] - lse;
-        const float p = __expf(lp);
-        dz[j] = (p - (j == a ? 1.f : 0.f)) * pg_adv + entropy_cost * p * (lp + Hn);
-      }
-      dvalues[idx] = -baseline_cost * err;
-      l_pg += (lse - zt[a]) * pg_adv;
-      l_bl += 0.5f * err * err;
-      l_ent -= Hn;
+      loss_step<false>(zt, A, act_s[tid], nv, sig * nv + mu, vs_s[tid], vs_s[tid + 1],
+                       p_s[tid], r_s[tid], disc_s[tid], mu, cs.rsig, baseline_cost,
+                       entropy_cost, static_cast<int64_t>(c0 + tid) * B + b, dlogits,
+                       dvalues, tk.vs_out, nullptr, l);
     }
   }
 
   // ---- the column's loss sums, then the last workgroup's fixed-order total
-  // (the hand-off of learner_head_fwd: sc1 partials, one ticket, re-armed)
-  l_pg = wave_sum(l_pg);
-  l_bl = wave_sum(l_bl);
-  l_ent = wave_sum(l_ent);
-  if (lane == 0) {
-    red[0][wave] = l_pg;
-    red[1][wave] = l_bl;
-    red[2][wave] = l_ent;
-  }
+  reduce_to_waves(l, red);
+  if (tid == 0) last_s = publish_column(partial, ticket, b, sum_waves(red));
   __syncthreads();
-  if (tid == 0) {
-    float pg = 0.f, bl = 0.f, en = 0.f;
-    for (int w = 0; w < kHeadWaves; ++w) {
-      pg += red[0][w];
-      bl += red[1][w];
-      en += red[2][w];
-    }
-    __hip_atomic_store(partial + b * 3 + 0, pg, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __hip_atomic_store(partial + b * 3 + 1, bl, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __hip_atomic_store(partial + b * 3 + 2, en, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    const unsigned prev = __hip_atomic_fetch_add(ticket, 1u, __ATOMIC_RELAXED,
-                                                 __HIP_MEMORY_SCOPE_AGENT);
-    last_s = (prev == static_cast<unsigned>(gridDim.x) - 1);
-  }
-  __syncthreads();
-  if (last_s && tid == 0) {
-    float pg = 0.f, bl = 0.f, en = 0.f;
-    for (int j = 0; j < B; ++j) {  // fixed order: deterministic
-      pg += __hip_atomic_load(partial + j * 3 + 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      bl += __hip_atomic_load(partial + j * 3 + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      en += __hip_atomic_load(partial + j * 3 + 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    loss[1] = pg;
-    loss[2] = bl;
-    loss[3] = en;
-    loss[0] = pg + baseline_cost * bl + entropy_cost * en;
-    __hip_atomic_store(ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // next launch
-  }
+  if (last_s && tid == 0) total_loss(partial, ticket, B, baseline_cost, entropy_cost, loss);
 }
 
 // dcore [N1, H] = g (dlogits W_p^T + dv W_b[:, task]^T) (rows >= Ng get
@@ -981,10 +689,9 @@ __global__ __launch_bounds__(256) void relu_mask_bf16_kernel(
 
 }  // namespace
 
+// (word counts in int, as the layouts: callers bound T and the tile first)
 size_t learner_head_fwd_smem(int T, int A) {
-  const int maxc = (A + 1 <= 16) ? 16 : 32;
-  return sizeof(float) * (256 * maxc + 64 + (T + 1) * (A + 1) + T * A + 4 * T +
-                          1 + 3 * T);
+  return sizeof(float) * HeadLds(A + 1 <= 16 ? 16 : kMaxA + 1, T, A).total;
 }
 
 int learner_head_fwd_max_unroll(int A) {
@@ -994,6 +701,23 @@ int learner_head_fwd_max_unroll(int A) {
   if (base + kHeadStaticLds > kLdsPerWorkgroup) return 0;
   return static_cast<int>((kLdsPerWorkgroup - kHeadStaticLds - base) / per_step);
 }
+
+namespace {
+// The launch both head kernels share: the dynamic-LDS attribute past the
+// 64 KB default, one workgroup per column.
+template <typename Kern, typename... Args>
+hipError_t head_fwd_launch(Kern kern, int B, size_t smem, hipStream_t stream,
+                           Args... args) {
+  if (smem > 64 * 1024) {
+    const hipError_t e = hipFuncSetAttribute(
+        reinterpret_cast<const void*>(kern),
+        hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(smem));
+    if (e != hipSuccess) return e;
+  }
+  hipLaunchKernelGGL(kern, dim3(B), dim3(kHeadThreads), smem, stream, args...);
+  return hipGetLastError();
+}
+}  // namespace
 
 hipError_t learner_head_fwd_launch(const float* core, const float* wp, const float* bp,
                                    const float* wb, const float* bb,
@@ -1006,22 +730,12 @@ hipError_t learner_head_fwd_launch(const float* core, const float* wp, const flo
                                    unsigned* ticket, float* loss, const HeadTasks& tk,
                                    hipStream_t stream) {
   if (T < 1 || T > learner_head_fwd_max_unroll(A)) return hipErrorInvalidValue;
-  const size_t smem = learner_head_fwd_smem(T, A);
-  auto k16 = learner_head_fwd_kernel<16>;
-  auto k32 = learner_head_fwd_kernel<kMaxA + 1>;
-  auto kern = (A + 1 <= 16) ? k16 : k32;
-  if (smem > 64 * 1024) {
-    const hipError_t e = hipFuncSetAttribute(
-        reinterpret_cast<const void*>(kern),
-        hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(smem));
-    if (e != hipSuccess) return e;
-  }
-  hipLaunchKernelGGL(kern, dim3(B), dim3(kHeadThreads), smem, stream, core, wp,
-                     bp, wb, bb, behaviour, actions, rewards, done, T, B, A,
-                     discounting, clip_mode, clip_rho, clip_pg_rho,
-                     baseline_cost, entropy_cost, dlogits, dvalues, partial,
-                     ticket, loss, tk);
-  return hipGetLastError();
+  return head_fwd_launch(A + 1 <= 16 ? learner_head_fwd_kernel<16>
+                                     : learner_head_fwd_kernel<kMaxA + 1>,
+                         B, learner_head_fwd_smem(T, A), stream, core, wp, bp, wb, bb,
+                         behaviour, actions, rewards, done, T, B, A, discounting,
+                         clip_mode, clip_rho, clip_pg_rho, baseline_cost, entropy_cost,
+                         dlogits, dvalues, partial, ticket, loss, tk);
 }
 
 namespace {
@@ -1031,9 +745,7 @@ bool head_tile_ok(int tc) { return tc >= 16 && tc <= kHeadThreads && tc % 16 == 
 }  // namespace
 
 size_t learner_head_fwd_tiled_smem(int TC, int A) {
-  return sizeof(float) * (256 * head_tiled_maxc(A) + 64 +
-                          static_cast<size_t>(TC + 1) * (A + 1) +
-                          static_cast<size_t>(TC) * A + 8 * static_cast<size_t>(TC));
+  return sizeof(float) * HeadTiledLds(head_tiled_maxc(A), TC, A).total;
 }
 
 bool learner_head_fwd_tiled_fits(int TC, int A) {
@@ -1063,24 +775,14 @@ hipError_t learner_head_fwd_tiled_launch(
   if (T < 1 || B < 1 || A < 1 || A > kTiledMaxA || !head_tile_ok(time_tile) ||
       !learner_head_fwd_tiled_fits(time_tile, A))
     return hipErrorInvalidValue;
-  const size_t smem = learner_head_fwd_tiled_smem(time_tile, A);
-  auto k16 = learner_head_fwd_tiled_kernel<16>;
-  auto k32 = learner_head_fwd_tiled_kernel<32>;
-  auto k64 = learner_head_fwd_tiled_kernel<64>;
   const int maxc = head_tiled_maxc(A);
-  auto kern = maxc == 16 ? k16 : (maxc == 32 ? k32 : k64);
-  if (smem > 64 * 1024) {
-    const hipError_t e = hipFuncSetAttribute(
-        reinterpret_cast<const void*>(kern),
-        hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(smem));
-    if (e != hipSuccess) return e;
-  }
-  hipLaunchKernelGGL(kern, dim3(B), dim3(kHeadThreads), smem, stream, core, wp,
-                     bp, wb, bb, behaviour, actions, rewards, done, T, B, A,
-                     discounting, clip_mode, clip_rho, clip_pg_rho,
-                     baseline_cost, entropy_cost, dlogits, dvalues, partial,
-                     ticket, loss, tk, time_tile);
-  return hipGetLastError();
+  return head_fwd_launch(maxc == 16   ? learner_head_fwd_tiled_kernel<16>
+                         : maxc == 32 ? learner_head_fwd_tiled_kernel<32>
+                                      : learner_head_fwd_tiled_kernel<64>,
+                         B, learner_head_fwd_tiled_smem(time_tile, A), stream, core, wp, bp,
+                         wb, bb, behaviour, actions, rewards, done, T, B, A, discounting,
+                         clip_mode, clip_rho, clip_pg_rho, baseline_cost, entropy_cost,
+                         dlogits, dvalues, partial, ticket, loss, tk, time_tile);
 }
 
 int head_bwd_maxc(int A1) { return A1 <= 16 ? 16 : (A1 <= 32 ? 32 : 64); }

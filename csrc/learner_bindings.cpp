@@ -106,22 +106,18 @@ std::vector<at::Tensor> head_fwd_impl(
   const float* rew1 = rewards.data_ptr<float>() + B;
   const uint8_t* done1 = mask_ptr(done) + B;
   unsigned* tick = reinterpret_cast<unsigned*>(ticket.data_ptr<int>());
-  const hipError_t err = tiled
-      ? sa::learner_head_fwd_tiled_launch(
-            core.data_ptr<float>(), wp.data_ptr<float>(), bp.data_ptr<float>(),
-            wb.data_ptr<float>(), bb.data_ptr<float>(), beh1, act1, rew1, done1, T,
-            B, A, (float)discounting, (int)clip_mode, (float)clip_rho,
-            (float)clip_pg_rho, (float)baseline_cost, (float)entropy_cost,
-            dlogits.data_ptr<float>(), dvalues.data_ptr<float>(),
-            partial.data_ptr<float>(), tick, loss.data_ptr<float>(), tk,
-            (int)time_tile, stream())
-      : sa::learner_head_fwd_launch(
-            core.data_ptr<float>(), wp.data_ptr<float>(), bp.data_ptr<float>(),
-            wb.data_ptr<float>(), bb.data_ptr<float>(), beh1, act1, rew1, done1, T,
-            B, A, (float)discounting, (int)clip_mode, (float)clip_rho,
-            (float)clip_pg_rho, (float)baseline_cost, (float)entropy_cost,
-            dlogits.data_ptr<float>(), dvalues.data_ptr<float>(),
-            partial.data_ptr<float>(), tick, loss.data_ptr<float>(), tk, stream());
+  // the operands both launchers share, then each one's own tail
+  auto launch = [&](auto fn, auto... tail) {
+    return fn(core.data_ptr<float>(), wp.data_ptr<float>(), bp.data_ptr<float>(),
+              wb.data_ptr<float>(), bb.data_ptr<float>(), beh1, act1, rew1, done1, T, B,
+              A, (float)discounting, (int)clip_mode, (float)clip_rho, (float)clip_pg_rho,
+              (float)baseline_cost, (float)entropy_cost, dlogits.data_ptr<float>(),
+              dvalues.data_ptr<float>(), partial.data_ptr<float>(), tick,
+              loss.data_ptr<float>(), tk, tail...);
+  };
+  const hipError_t err =
+      tiled ? launch(sa::learner_head_fwd_tiled_launch, (int)time_tile, stream())
+            : launch(sa::learner_head_fwd_launch, stream());
   TORCH_CHECK(err == hipSuccess, tiled ? "learner_head_fwd_tiled" : "learner_head_fwd",
               " launch failed: ", hipGetErrorString(err));
   if (want_vs) return {loss, dlogits, dvalues, vs};

@@ -90,6 +90,21 @@ def test_compute_loss_leaves_fused_path_at_64_actions(calls):
   assert calls == [('vtrace_loss',)]
 
 
+def test_lds_limits_of_the_built_extension():
+  """The unroll limits and default tiles that follow from the kernels' LDS
+  layouts (160 KB a workgroup, 8400 bytes of static arrays): pinned, since
+  a layout that moves a tile moves the bits of every tiled run.  The tiles
+  are the ones recorded in profiles/experiments.md."""
+  from scalable_agent_amd import ops
+  if not ops.available():
+    pytest.skip('the HIP extension is not built')
+  ext = ops.ext()
+  unroll = {9: 1334, 31: 436}
+  assert {A: ext.learner_head_max_unroll(A) for A in unroll} == unroll
+  tiles = {9: 1024, 18: 672, 31: 416, 40: 240, 63: 160}
+  assert {A: ext.learner_head_tile_auto(A) for A in tiles} == tiles
+
+
 def test_value_heads_count_against_the_64_columns(calls):
   """A + K <= 64 holds for the tiled kernel's callers too."""
   data = _batch(8, 40)._replace(level_name=torch.zeros(2, dtype=torch.int64))
