@@ -24,7 +24,8 @@
 // the row tile's last ticket acquires (agent scope, one lane, drain, barrier)
 // and finishes the tile: one wave per row recomputes nothing of the LSTM, it
 // reads the row's complete h2 and forms the heads exactly as
-// actor_head_sample_kernel does (lane-local 4-term partials, butterfly), so
+// actor_head_sample_kernel does (head_sample.h: lane-local 4-term partials,
+// butterfly for A <= 32, reduce-scatter for 33..63), so
 // the sums have one fixed order and there are no per-workgroup head partials
 // to re-read (they would be 64 x 16 x (A + 1) floats per tile against the
 // 16 KB of h2 the finisher needs anyway for the packing).  The ticket words
@@ -35,8 +36,8 @@
 // h_in is every workgroup's A operand, so h2 is a distinct buffer.  The
 // board's commit target may be h_in / c_in themselves: the finisher writes a
 // tile's rows only after every reader of those rows has taken its ticket.
+#include "head_sample.h"
 #include "launchers.h"
-#include "philox.h"
 
 namespace sa {
 namespace {
@@ -44,7 +45,6 @@ namespace {
 typedef float f4v __attribute__((ext_vector_type(4)));
 
 constexpr int kH = 256;
-constexpr int kMaxA = 32;
 constexpr int kNW = 8;       // waves per workgroup
 constexpr int kNSMax = 20;   // MFMA k-steps per wave: (K + 256) / 4 / 8 <= 20
 constexpr int kRows = 16;    // rows per tile
@@ -81,50 +81,15 @@ struct ActorCoreArgs {
 __device__ __forceinline__ float sigm(float x) { return 1.f / (1.f + __expf(-x)); }
 
 // heads + Gumbel-max sample (+ board commit / packing) of one finished row
+template <int W>
 __device__ __forceinline__ void finish_row(const ActorCoreArgs& a, int row, int lane,
                                            unsigned long long offset) {
   const int A = a.A;
   const float4 x = reinterpret_cast<const float4*>(a.h2 + static_cast<int64_t>(row) * kH)[lane];
-  const float* w0 = a.wp + (4 * lane) * A;
-  float acc[kMaxA + 1];
-#pragma unroll
-  for (int j = 0; j < kMaxA; ++j)
-    acc[j] = j < A ? x.x * w0[j] + x.y * w0[A + j] + x.z * w0[2 * A + j] + x.w * w0[3 * A + j]
-                   : 0.f;
-  const float* v0 = a.wb + static_cast<int64_t>(4 * lane) * a.Kv;
-  acc[kMaxA] = x.x * v0[0] + x.y * v0[a.Kv] + x.z * v0[2 * static_cast<int64_t>(a.Kv)] +
-               x.w * v0[3 * static_cast<int64_t>(a.Kv)];
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) {
-#pragma unroll
-    for (int j = 0; j <= kMaxA; ++j)
-      if (j < A || j == kMaxA) acc[j] += __shfl_xor(acc[j], m, 64);
-  }
-  float mine = -INFINITY;
-#pragma unroll
-  for (int j = 0; j < kMaxA; ++j)
-    if (j == lane) mine = acc[j];
-  float key = -INFINITY;
-  if (lane < A) {
-    mine += a.bp[lane];
-    a.logits[static_cast<int64_t>(row) * A + lane] = mine;
-    const uint4 r = philox4x32_10(
-        make_uint4((unsigned)row, (unsigned)lane, (unsigned)offset, (unsigned)(offset >> 32)),
-        make_uint2((unsigned)a.seed, (unsigned)(a.seed >> 32)));
-    const float u = ((r.x >> 8) + 0.5f) * (1.0f / 16777216.0f);  // (0,1)
-    key = mine - __logf(-__logf(u));
-  }
-  int idx = lane;
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) {
-    const float ok = __shfl_xor(key, m, 64);
-    const int oi = __shfl_xor(idx, m, 64);
-    if (ok > key || (ok == key && oi < idx)) {
-      key = ok;
-      idx = oi;
-    }
-  }
-  const float base = acc[kMaxA] + a.bb[0];
+  const HeadSample hs = head_sample_row<W, false>(x, a.wp, a.bp, a.wb, a.bb, a.Kv, a.logits, A,
+                                                  a.seed, offset, row, lane);
+  const float mine = hs.logit, base = hs.baseline;
+  const int idx = hs.action;
   if (lane == 0) {
     a.baseline[row] = base;
     a.action[row] = idx;
@@ -148,6 +113,9 @@ __device__ __forceinline__ void finish_row(const ActorCoreArgs& a, int row, int 
   if (a.masked_only) __threadfence_system();
 }
 
+// W: the finisher's head accumulator width (32: A <= 32, 64: A <= 63); the
+// launcher picks the instance, nothing before the finisher depends on it
+template <int W>
 __global__ __launch_bounds__(64 * kNW) void actor_core_step_kernel(ActorCoreArgs a) {
   __shared__ f4v red[kNW][64];
   __shared__ float g_s[kRows][17];
@@ -259,7 +227,7 @@ __global__ __launch_bounds__(64 * kNW) void actor_core_step_kernel(ActorCoreArgs
     offset = __hip_atomic_load(a.counter, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   for (int rr = wave; rr < kRows; rr += kNW) {
     const int row = r0 + rr;
-    if (row < R) finish_row(a, row, lane, offset);
+    if (row < R) finish_row<W>(a, row, lane, offset);
   }
   // the sampler's counter pair {offset, waves done}: every finishing wave
   // counts itself after its sampling; the last one of the launch stores
@@ -342,8 +310,9 @@ void actor_core_step_launch(const ActorCoreStep& p, hipStream_t stream) {
   a.M = p.M;
   a.slot_dw = p.slot_dw;
   a.masked_only = p.masked_only;
-  hipLaunchKernelGGL(actor_core_step_kernel, dim3(kH / 4, (p.R + kRows - 1) / kRows),
-                     dim3(64 * kNW), 0, stream, a);
+  auto kernel = p.A <= 32 ? actor_core_step_kernel<32> : actor_core_step_kernel<64>;
+  hipLaunchKernelGGL(kernel, dim3(kH / 4, (p.R + kRows - 1) / kRows), dim3(64 * kNW), 0, stream,
+                     a);
 }
 
 }  // namespace sa

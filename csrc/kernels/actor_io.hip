@@ -4,23 +4,23 @@
 //
 // One 64-lane wavefront per batch row.  Lane l holds h[4l..4l+3] (one 16-byte
 // load), forms its 4-term partial dot product for every output column and the
-// row's A+1 sums are finished with a butterfly (every lane ends with every
-// logit; no LDS, no barriers).  Lane a < A then draws u_a from Philox4x32-10
+// row's A+1 sums are finished across the wave (head_sample.h: a butterfly for
+// A <= 32, a reduce-scatter for 33..63; no LDS, no barriers).  Lane a < A
+// then draws u_a from Philox4x32-10
 // (key = seed, counter = (row, a, offset)) and the action is the Gumbel-max
 // argmax_a (logit_a - log(-log u_a)), reduced across the wave with the lower
 // index winning ties - an exact sample from softmax(logits), reproducible for
 // a given (seed, offset) whatever the batch composition of the other rows.
 // With offset_ptr the offset is read from device memory, so a captured
 // inference graph draws fresh samples on every replay (the graph bumps it).
+#include "head_sample.h"
 #include "launchers.h"
-#include "philox.h"
 
 namespace sa {
 namespace {
 
-constexpr int kMaxA = 32;
-
 // heads + Gumbel-max sample of one row (one wave)
+template <int W>
 __device__ __forceinline__ void sample_row(
     const float* __restrict__ h, const float* __restrict__ wp,
     const float* __restrict__ bp, const float* __restrict__ wb,
@@ -28,52 +28,16 @@ __device__ __forceinline__ void sample_row(
     float* __restrict__ baseline, int64_t* __restrict__ action, int A,
     unsigned long long seed, unsigned long long offset, int row, int lane) {
   const float4 x = reinterpret_cast<const float4*>(h + (int64_t)row * 256)[lane];
-  const float* w0 = wp + (4 * lane) * A;
-  float acc[kMaxA + 1];
-#pragma unroll
-  for (int a = 0; a < kMaxA; ++a)
-    acc[a] = a < A ? x.x * w0[a] + x.y * w0[A + a] + x.z * w0[2 * A + a] +
-                         x.w * w0[3 * A + a]
-                   : 0.f;
-  const float4 wv = reinterpret_cast<const float4*>(wb)[lane];
-  acc[kMaxA] = x.x * wv.x + x.y * wv.y + x.z * wv.z + x.w * wv.w;
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) {
-#pragma unroll
-    for (int a = 0; a <= kMaxA; ++a)
-      if (a < A || a == kMaxA) acc[a] += __shfl_xor(acc[a], m, 64);
-  }
-  float mine = -INFINITY;
-#pragma unroll
-  for (int a = 0; a < kMaxA; ++a)
-    if (a == lane) mine = acc[a];
-  float key = -INFINITY;
-  if (lane < A) {
-    mine += bp[lane];
-    logits[(int64_t)row * A + lane] = mine;
-    const uint4 r = philox4x32_10(
-        make_uint4((unsigned)row, (unsigned)lane, (unsigned)offset,
-                   (unsigned)(offset >> 32)),
-        make_uint2((unsigned)seed, (unsigned)(seed >> 32)));
-    const float u = ((r.x >> 8) + 0.5f) * (1.0f / 16777216.0f);  // (0,1)
-    key = mine - __logf(-__logf(u));
-  }
-  int idx = lane;
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) {
-    const float ok = __shfl_xor(key, m, 64);
-    const int oi = __shfl_xor(idx, m, 64);
-    if (ok > key || (ok == key && oi < idx)) {
-      key = ok;
-      idx = oi;
-    }
-  }
+  const HeadSample s =
+      head_sample_row<W, true>(x, wp, bp, wb, bb, 1, logits, A, seed, offset, row, lane);
   if (lane == 0) {
-    baseline[row] = acc[kMaxA] + bb[0];
-    action[row] = idx;
+    baseline[row] = s.baseline;
+    action[row] = s.action;
   }
 }
 
+// W = 32: A <= 32; W = 64: A <= 63 (the launcher picks)
+template <int W>
 __global__ __launch_bounds__(256) void actor_head_sample_kernel(
     const float* __restrict__ h, const float* __restrict__ wp,
     const float* __restrict__ bp, const float* __restrict__ wb,
@@ -84,7 +48,8 @@ __global__ __launch_bounds__(256) void actor_head_sample_kernel(
   const int lane = threadIdx.x & 63;
   if (offset_ptr != nullptr) offset = *offset_ptr;  // graph-replayed stream
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (row < B) sample_row(h, wp, bp, wb, bb, logits, baseline, action, A, seed, offset, row, lane);
+  if (row < B)
+    sample_row<W>(h, wp, bp, wb, bb, logits, baseline, action, A, seed, offset, row, lane);
   // advance: the stream's counter pair {offset, waves done} moves to the next
   // offset in this launch (no separate add kernel in the board's graph).
   // Every wave counts itself once after its sampling (which consumed the
@@ -182,7 +147,7 @@ void board_epilogue_launch(const void* const* src, const int* per_dw, const int*
   hipLaunchKernelGGL(board_epilogue_kernel, dim3(R), dim3(256), 0, stream, a);
 }
 
-int actor_head_max_actions() { return kMaxA; }
+int actor_head_max_actions() { return kActorMaxActions; }
 
 void actor_head_sample_launch(const float* h, const float* wp, const float* bp,
                               const float* wb, const float* bb, float* logits,
@@ -191,7 +156,8 @@ void actor_head_sample_launch(const float* h, const float* wp, const float* bp,
                               unsigned long long* offset_ptr, int advance,
                               hipStream_t stream) {
   if (B <= 0) return;
-  hipLaunchKernelGGL(actor_head_sample_kernel, dim3((B + 3) / 4), dim3(256), 0,
+  auto kernel = A <= 32 ? actor_head_sample_kernel<32> : actor_head_sample_kernel<64>;
+  hipLaunchKernelGGL(kernel, dim3((B + 3) / 4), dim3(256), 0,
                      stream, h, wp, bp, wb, bb, logits, baseline, action, B, A,
                      seed, offset, offset_ptr, advance);
 }

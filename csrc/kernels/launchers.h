@@ -205,7 +205,7 @@ void relu_mask_bf16_launch(void* dx, const void* x, int64_t n,
 // ---- actor_io.hip ----------------------------------------------------------
 // Actor inference head: logits [B,A] = h Wp + bp, baseline [B] = h Wb + bb,
 // action [B] ~ Categorical(softmax(logits)) by Gumbel-max over Philox4x32-10
-// (key = seed, counter = (row, a, offset)).  h fp32 [B,256], A <= 32.
+// (key = seed, counter = (row, a, offset)).  h fp63 [B,256], A <= 63.
 int actor_head_max_actions();
 // inference-board epilogue (actor_io.hip): masked state update + slot-major
 // output packing in one launch
@@ -224,7 +224,7 @@ void actor_head_sample_launch(const float* h, const float* wp, const float* bp,
 // ---- actor_core.hip --------------------------------------------------------
 // The actor's T = 1 core step in one launch (exact fp32): x-projection +
 // LSTM-256 step + heads + Gumbel-max sample (+ the board epilogue when `out`
-// is set).  K % 16 == 0, K <= min(kmax, actor_core_max_k()), A <= 32.
+// is set).  K % 16 == 0, K <= min(kmax, actor_core_max_k()), A <= 63.
 struct ActorCoreStep {
   const float* h_aug;   // [R, ld]: [relu(fc), clip(r), one_hot(a), instr|0]
   const uint8_t* done;  // [R]

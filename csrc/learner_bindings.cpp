@@ -256,7 +256,7 @@ std::vector<at::Tensor> actor_head_sample(at::Tensor h, at::Tensor wp, at::Tenso
   TORCH_CHECK(h.dim() == 2 && h.size(1) == 256, "h must be [B,256]");
   TORCH_CHECK(wp.dim() == 2 && wp.size(0) == 256, "policy w must be [256,A]");
   const int B = h.size(0), A = wp.size(1);
-  TORCH_CHECK(A >= 1 && A <= sa::actor_head_max_actions(), "1 <= num_actions <= 32");
+  TORCH_CHECK(A >= 1 && A <= sa::actor_head_max_actions(), "1 <= num_actions <= 63");
   TORCH_CHECK(bp.numel() == A && wb.numel() == 256 && bb.numel() == 1,
               "one value head");
   TORCH_CHECK(reinterpret_cast<uintptr_t>(h.data_ptr()) % 16 == 0 &&
@@ -381,7 +381,7 @@ std::vector<at::Tensor> actor_core_step(
   TORCH_CHECK(wp.dim() == 2 && wp.size(0) == 256 && wb.dim() == 2 && wb.size(0) == 256,
               "heads must be [256, A] / [256, Kv]");
   const int64_t A = wp.size(1), Kv = wb.size(1);
-  TORCH_CHECK(A >= 1 && A <= sa::actor_head_max_actions(), "1 <= num_actions <= 32");
+  TORCH_CHECK(A >= 1 && A <= sa::actor_head_max_actions(), "1 <= num_actions <= 63");
   TORCH_CHECK(bp.numel() == A && Kv >= 1 && bb.numel() == Kv, "head biases");
   TORCH_CHECK(257 + A <= K, "h_aug narrower than [h, r, one_hot(a)]");
   TORCH_CHECK(tickets.scalar_type() == at::kInt && tickets.numel() >= (R + 15) / 16,

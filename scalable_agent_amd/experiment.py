@@ -164,7 +164,7 @@ def _log_actor_core(flags, model):
     log.info('actor inference core: %s', used)
   else:
     log.info('actor inference core: %s (--actor_core=%s needs an fp32 HIP '
-             'agent on a GPU with at most 32 actions)', used, asked)
+             'agent on a GPU with at most 63 actions)', used, asked)
 
 
 class EpisodeLogger(object):

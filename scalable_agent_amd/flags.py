@@ -113,7 +113,9 @@ def build_parser() -> argparse.ArgumentParser:
                       'x-projection GEMM, LSTM step and heads + sampler '
                       'kernels; fused = ONE kernel after the torso-FC GEMM '
                       '(on an inference board it also commits the state and '
-                      'packs the outputs).  bf16 inference runs ops.')
+                      'packs the outputs).  Both take up to 63 actions (with '
+                      'more the actors sample with torch.multinomial).  bf16 '
+                      'inference runs ops.')
   p.add_argument('--inference_device', default='auto',
                  help='Device of the actor-inference model: auto = the '
                       'learner device; e.g. cuda:1 or cpu.')

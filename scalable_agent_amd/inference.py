@@ -7,7 +7,9 @@ weights after every update with one device-to-device copy of the flat buffer,
 so an inference batch never reads half-updated weights.  Inference runs on a
 dedicated HIP stream, concurrently with the learner stream.  On the HIP
 backend the heads and the categorical sample are one kernel (actor_io.hip,
-Gumbel-max over a device-side Philox stream).
+Gumbel-max over a device-side Philox stream) for up to
+ops.heads.ACTOR_MAX_ACTIONS (63) actions; a larger action set samples with
+torch.multinomial from a torch.Generator.
 
 `make_batched_infer` wraps it with the C++ dynamic batcher: actor threads call
 it with batch-1 numpy arrays; a runner thread executes batches of up to
@@ -19,6 +21,7 @@ pinned slab, and one stream synchronisation ends the batch (SURVEY.md §2.2
 "beyond the reference").
 """
 
+import logging
 import threading
 import time
 
@@ -28,6 +31,20 @@ import torch
 from . import dynamic_batching
 from .optim import FlatParams
 from .structs import StepOutput, StepOutputInfo
+
+
+log = logging.getLogger('scalable_agent_amd')
+_torch_sampler_logged = False
+
+
+def _log_torch_sampler(num_actions, limit):
+  """Once per process: why HIP actors do not use the device-side sampler."""
+  global _torch_sampler_logged
+  if not _torch_sampler_logged:
+    _torch_sampler_logged = True
+    log.info('actor inference samples with torch.multinomial: %d actions, the '
+             'HIP heads + sampler kernels take at most %d (an inference board '
+             'runs its Python serve loop)', num_actions, limit)
 
 
 class InferenceModel(object):
@@ -42,8 +59,15 @@ class InferenceModel(object):
     self._lock = threading.Lock()
     self._stream = (torch.cuda.Stream(self.device)
                     if self.device.type == 'cuda' else None)
-    if self.device.type == 'cuda' and getattr(agent, 'backend', '') == 'hip':
-      from .ops.heads import PhiloxStream
+    hip = self.device.type == 'cuda' and getattr(agent, 'backend', '') == 'hip'
+    if hip:
+      # the sampler kernels' action limit; past it the agent samples with
+      # torch.multinomial, which takes a torch.Generator
+      from .ops.heads import ACTOR_MAX_ACTIONS, PhiloxStream
+      if agent.num_actions > ACTOR_MAX_ACTIONS:
+        _log_torch_sampler(agent.num_actions, ACTOR_MAX_ACTIONS)
+        hip = False
+    if hip:
       self._gen = PhiloxStream(seed, device=self.device)
     else:
       self._gen = torch.Generator(device=self.device).manual_seed(seed)
@@ -58,6 +82,14 @@ class InferenceModel(object):
   @property
   def stream(self):
     return self._stream
+
+  @property
+  def device_sampler(self):
+    """True when the sampler's state lives on the device (a PhiloxStream): a
+    captured step then draws fresh samples on every replay, also when it is
+    launched from C++."""
+    from .ops.heads import PhiloxStream
+    return isinstance(self._gen, PhiloxStream)
 
   def publish(self, flat_params, version=None):
     """Copies the learner's flat parameter buffer into the snapshot.
@@ -184,7 +216,8 @@ class StagedBatchedInfer(object):
     self.max_batch = int(max_batch)
     if graphs is None:
       graphs = (model.device.type == 'cuda' and
-                getattr(model.agent, 'backend', '') == 'hip')
+                getattr(model.agent, 'backend', '') == 'hip' and
+                getattr(model, 'device_sampler', True))
     self.graphs = bool(graphs)
     self._bucket_graphs = {}
     self._pool = None
@@ -414,7 +447,8 @@ class VectorInfer(object):
     dev = model.device
     self.cuda = dev.type == 'cuda'
     if use_graph is None:
-      use_graph = self.cuda and getattr(model.agent, 'backend', '') == 'hip'
+      use_graph = (self.cuda and getattr(model.agent, 'backend', '') == 'hip'
+                   and getattr(model, 'device_sampler', True))
     self.use_graph = bool(use_graph) and self.cuda
     shapes = {'frame': tuple(frame_shape), 'instr_ids': (int(instr_len),)}
     layout, off = [], 0

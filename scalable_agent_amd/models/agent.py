@@ -475,7 +475,8 @@ class Agent(nn.Module):
       cache['w16'] = (
           torch.empty(self.linear_w.shape, dtype=bf, device=dev),
           torch.empty(k_max, self.lstm_kernel.shape[1], dtype=bf, device=dev))
-    if self.actor_core == 'fused':
+    from ..ops.heads import ACTOR_MAX_ACTIONS
+    if self.actor_core == 'fused' and self.num_actions <= ACTOR_MAX_ACTIONS:
       # [W_x[:K_max]; W_h] in the fused core step's B-operand layout
       from ..ops import actor_core
       k_max = actor_core.packed_rows(self.num_actions)
@@ -513,12 +514,13 @@ class Agent(nn.Module):
   def actor_core_fused(self, generator, cuda=True):
     """True when `actor_core='fused'` is honoured for a T = 1 no-grad step
     of CUDA tensors sampled from `generator`: fp32 HIP agent whose fused core
-    applies, at most 32 actions, a PhiloxStream.  Otherwise the ops path
-    runs."""
-    from ..ops.heads import PhiloxStream
+    applies, at most ops.heads.ACTOR_MAX_ACTIONS (63) actions, a
+    PhiloxStream.  Otherwise the ops path runs."""
+    from ..ops.heads import ACTOR_MAX_ACTIONS, PhiloxStream
     return (self.actor_core == 'fused' and self.backend == 'hip' and cuda and
             self.compute_dtype == torch.float32 and self.fused_core_ready() and
-            self.num_actions <= 32 and isinstance(generator, PhiloxStream))
+            self.num_actions <= ACTOR_MAX_ACTIONS and
+            isinstance(generator, PhiloxStream))
 
   def _fused_step(self, actions, env_outputs, core_state, generator, epilogue):
     """The T = 1 actor step with the fused core: torso, the torso-FC GEMM
@@ -592,11 +594,13 @@ class Agent(nn.Module):
 
   def _fused_sampler_ready(self, core_out, task_ids, generator):
     """Heads + Gumbel-max sampling as one HIP kernel (actor_io.hip) when the
-    caller drives a device-side PhiloxStream.  A multi-head agent without
+    caller drives a device-side PhiloxStream, for at most
+    ops.heads.ACTOR_MAX_ACTIONS (63) actions.  A multi-head agent without
     task ids reports value head 0, as `heads` does."""
-    from ..ops.heads import PhiloxStream
+    from ..ops.heads import ACTOR_MAX_ACTIONS, PhiloxStream
     return (isinstance(generator, PhiloxStream) and self.backend == 'hip' and
-            core_out.is_cuda and task_ids is None and self.num_actions <= 32)
+            core_out.is_cuda and task_ids is None and
+            self.num_actions <= ACTOR_MAX_ACTIONS)
 
   def _value_head0(self):
     """(baseline_w, baseline_b) of value head 0, contiguous [256, 1] / [1]:

@@ -63,8 +63,9 @@ def actor_core_step(h_aug, done, c_in, h_in, wpk, b_lstm, policy_w, policy_b,
                     ticket_words=None):
   """h_aug [R, K] fp32 (ops.core.core_input_f32), done [R] bool / uint8,
   state (c_in, h_in) [R, 256], wpk from actor_core_pack, b_lstm [1024],
-  heads policy_w [256, A] / policy_b / baseline_w [256, Kv] / baseline_b
-  (value head 0 is reported), stream a PhiloxStream (advanced by one).
+  heads policy_w [256, A] (A <= heads.ACTOR_MAX_ACTIONS) / policy_b /
+  baseline_w [256, Kv] / baseline_b (value head 0 is reported), stream a
+  PhiloxStream (advanced by one).
   -> (action [R] int64, logits [R, A], baseline [R], c2, h2).
 
   epilogue (a BoardEpilogue): c_in / h_in also take c2 / h2 in place where

@@ -25,6 +25,11 @@ import torch
 from . import grad_sink
 from ._ext import ext
 
+# largest action count of the actor inference kernels (actor_heads_sample and
+# the fused actor core step); the time-tiled learner heads stop at the same
+# number
+ACTOR_MAX_ACTIONS = 63
+
 _CLIP = {'abs_one': 0, 'soft_asymmetric': 1}
 _TICKETS = {}
 # forward launches per head kernel (tests check which one a caller selected)
@@ -167,7 +172,9 @@ def actor_heads_sample(core_out, policy_w, policy_b, baseline_w, baseline_b,
                        stream):
   """Actor inference heads + sampling in one kernel (actor_io.hip):
   core_out [B,256] f32 -> (action [B] int64, logits [B,A], baseline [B]).
-  `stream`: a PhiloxStream (advanced by one)."""
+  `stream`: a PhiloxStream (advanced by one).  A <= ACTOR_MAX_ACTIONS (a
+  32-wide kernel instance up to 32 actions, a 64-wide one above);
+  RuntimeError beyond."""
   args = (core_out.float().contiguous(), policy_w.contiguous(),
           policy_b.contiguous(), baseline_w.reshape(-1).contiguous(),
           baseline_b.reshape(-1).contiguous(), stream.seed)

@@ -179,6 +179,11 @@ class BoardServer(object):
     dev = model.device
     self.cuda = dev.type == 'cuda'
     self.use_graph = bool(use_graph) and self.cuda
+    if (getattr(model.agent, 'backend', '') == 'hip' and
+        not getattr(model, 'device_sampler', True)):
+      # a HIP agent past the sampler kernels' action limit draws from a
+      # torch.Generator (inference.py): eager steps, the Python serve loop
+      self.use_graph = False
     b = board
     # the board's input + output regions as host tensors (pinned on a GPU)
     self._host_in = torch.from_numpy(b.buf[b.HDR:b.HDR + b.in_bytes])
@@ -376,10 +381,14 @@ class BoardServer(object):
   def _native_ok(self):
     # the graphs' sampler must keep its state on the device (PhiloxStream of
     # the HIP backend): a torch.Generator needs CUDAGraph.replay()'s host
-    # prologue, which a C++ hipGraphLaunch does not run
-    return (self.use_graph and self.pinned and
+    # prologue, which a C++ hipGraphLaunch does not run (a HIP agent with
+    # more actions than the sampler kernels take holds one: inference.py)
+    if not (self.use_graph and self.pinned and
             os.environ.get('SA_BOARD_NATIVE', '1') != '0' and
-            getattr(self.model.agent, 'backend', '') == 'hip')
+            getattr(self.model.agent, 'backend', '') == 'hip'):
+      return False
+    from ..ops.heads import PhiloxStream
+    return isinstance(getattr(self.model, '_gen', None), PhiloxStream)
 
   def _start_native(self):
     from .. import ops
