@@ -399,6 +399,39 @@ std::vector<at::Tensor> wino_conv_pool_fwd(at::Tensor x, at::Tensor w, at::Tenso
   return {y, arg};
 }
 
+// Whole residual block (actor inference): y = conv2(relu(conv1(relu(x)) + b1))
+// + b2 + x [relu when last] in one launch (conv_wino.hip
+// wino_res_block_kernel), bitwise the two cf32_conv_fwd calls; {} when the
+// shape is not covered (nothing ran; the caller runs the two convs)
+std::vector<at::Tensor> res_block_fwd(at::Tensor x, at::Tensor w1, at::Tensor b1, at::Tensor w2,
+                                      at::Tensor b2, bool last) {
+  check_nhwc(x, "x");
+  check_w(w1);
+  check_w(w2);
+  TORCH_CHECK(x.scalar_type() == at::kFloat, "x must be float32");
+  const int64_t C = x.size(3);
+  for (const at::Tensor* w : {&w1, &w2})
+    TORCH_CHECK(w->size(0) == 3 && w->size(2) == C && w->size(3) == C,
+                "res_block_fwd: HWIO [3,3,C,C] weights for a C-channel map");
+  for (const at::Tensor* b : {&b1, &b2})
+    TORCH_CHECK(b->is_cuda() && b->scalar_type() == at::kFloat && b->is_contiguous() &&
+                    b->numel() == C, "bias");
+  if (C != 16 && C != 32) return {};
+  if (x.size(0) > sa::cf32::kResBlockMaxFrames || x.size(1) > INT_MAX || x.size(2) > INT_MAX)
+    return {};
+  const c10::DeviceGuard g(x.device());
+  auto y = at::empty(x.sizes(), x.options());
+  if (!sa::cf32::wino_res_block_launch(x.data_ptr<float>(), w1.data_ptr<float>(),
+                                       b1.data_ptr<float>(), w2.data_ptr<float>(),
+                                       b2.data_ptr<float>(), y.data_ptr<float>(),
+                                       static_cast<int>(x.size(0)), static_cast<int>(x.size(1)),
+                                       static_cast<int>(x.size(2)), static_cast<int>(C), last,
+                                       stream()))
+    return {};
+  check_launch("cf32_res_block_fwd");
+  return {y};
+}
+
 std::vector<at::Tensor> maxpool_fwd(at::Tensor x, int64_t pb_h, int64_t pb_w) {
   check_nhwc(x, "x");
   TORCH_CHECK(x.scalar_type() == at::kFloat && x.size(3) % 4 == 0, "maxpool: float32, C % 4 == 0");
@@ -474,6 +507,11 @@ void register_conv_f32_ops(pybind11::module& m) {
   m.def("cf32_conv_pool_fwd", &conv_pool_fwd);
   m.def("cf32_wino_conv_pool_fwd", &wino_conv_pool_fwd, arg("x"), arg("w"), arg("b"),
         arg("stages") = -1);
+  m.def("cf32_res_block_fwd", &res_block_fwd, arg("x"), arg("w1"), arg("b1"), arg("w2"),
+        arg("b2"), arg("last") = false);
+  // output rows per workgroup of cf32_res_block_fwd for a C-channel map of
+  // width W (0: no instance); tests cross every band seam with it
+  m.def("cf32_res_block_band", [](int C, int W) { return sa::cf32::wino_res_block_band(C, W); });
   m.def("cf32_maxpool_fwd", &maxpool_fwd);
   m.def("cf32_maxpool_bwd", &maxpool_bwd);
   m.def("cf32_relu_mask_", &relu_mask_);

@@ -114,6 +114,20 @@ int conv_cu_reserve(int r);
 // CUs the persistent grids are sized for now: 256 - 8 * conv_cu_reserve(-1).
 int conv_cus();
 bool wino_conv_launch(const ConvArgs& a, bool flip, hipStream_t s);
+// Whole residual block for actor inference (conv_wino.hip
+// wino_res_block_kernel), C = 16 or 32, fp32 NHWC:
+//   t = relu(conv1(relu(x)) + b1);  y = conv2(t) + b2 + x  [relu when last]
+// in one launch, t only in LDS; bitwise the two wino_conv_launch calls it
+// replaces.  False (nothing launched) where either of those would not run the
+// Winograd forward (tiny maps, oversize batches, SA_F32_WINO=0), where no
+// band instance fits the map's width, or above kResBlockMaxFrames images: the
+// caller then runs the two convs.
+constexpr int kResBlockMaxFrames = 512;
+// output rows per workgroup for a C-channel map of width W (0: no instance)
+int wino_res_block_band(int C, int W);
+bool wino_res_block_launch(const float* x, const float* w1, const float* b1, const float* w2,
+                           const float* b2, float* y, int N, int H, int W, int C, bool last,
+                           hipStream_t s);
 // Stage head with the 3x3/2 SAME max-pool fused (conv_wino.hip): x [N,H,W,Cin]
 // -> pooled [N,H/2,W/2,Cout] + argmax codes, the 3x3/1 conv + bias in
 // Winograd form, the pre-pool map only in LDS.  (Cin, Cout) = (16, 32) with

@@ -624,6 +624,11 @@ void allow_lds_w(Kern k, size_t bytes) {
 
 int g_wino_fault = 0;  // conv_wino_fault(): tests of the fail-loud hand-off
 
+// While set, run_wino_g answers whether it would run the shape and launches
+// nothing (wino_res_block_launch: the fused block declines exactly where
+// either conv of the two-launch form would leave the Winograd forward).
+thread_local bool t_wino_probe = false;
+
 template <int CIN, int COUT, int NH, int NW, int RT, int MAXC, int WPS, int FL = -1, int GH = 0,
           int GW = 0>
 bool run_wino_g(const ConvArgs& c, bool flip, hipStream_t s) {
@@ -647,6 +652,7 @@ bool run_wino_g(const ConvArgs& c, bool flip, hipStream_t s) {
   if (static_cast<int64_t>(c.N) * H * W * CIN * 4 > kMaxBufBytes || maxrows > 64 * NW)
     return false;
   if (bytes > 160 * 1024) return false;
+  if (t_wino_probe) return true;
   WinoArgs a{};
   a.src = static_cast<const float*>(c.src);
   a.w = c.w;
@@ -2984,7 +2990,327 @@ bool run_wino_bwd(const float* dy, const float* w, const float* x, const float* 
                                                   ws_floats, dw, db, s);
 }
 
+// ------------------------------------------------- fused residual block
+// One whole residual block of the deep torso for actor inference (small
+// no-grad batches, where every conv launch sits at its fixed cost):
+//   t = relu(conv1(relu(x)) + b1);  y = conv2(t) + b2 + x  [then relu]
+// in ONE launch, t only in LDS.  A workgroup owns a band of R output rows of
+// one image (all columns).  It stages the raw x rows y0 - 3 .. y0 + R + 2
+// (zero outside the image; conv1 applies the ReLU when it reads a patch, the
+// residual add reads the raw value), computes t for the tile rows that cover
+// rows y0 - 2 .. y0 + R + 1 (the band plus conv2's one-tile-row halo above
+// and below, conv1 recomputed there: (R + 4) / R of its work) into an LDS
+// image whose out-of-image rows and columns stay zero (conv2's SAME padding
+// pads t, not x), transforms w2 into the U buffer w1's transform occupied,
+// and computes y from the t image.  Workgroups are independent; the only
+// synchronisation is __syncthreads.
+//
+// Per output element the arithmetic is wino_conv_kernel's (the expressions
+// below are copies of its weight / input / output transforms, its MFMA
+// k-step order and its epilogue order: bias, residual, ReLU), so the result
+// is bitwise that of the two launches (tests/test_res_block_f32_gpu.py).
+struct ResBlockArgs {
+  const float* x;   // [N, H, W, C]
+  const float* w1;  // HWIO [3, 3, C, C]
+  const float* b1;  // [C]
+  const float* w2;
+  const float* b2;
+  float* y;         // [N, H, W, C]
+  int N, H, W, TY, TX, nbands, last;
+  float rTX, rWl;
+};
+
+// U = G g G^T of w into U_s as MFMA A fragments [16 xi][C/16][4 g][C][4]
+template <int C, int NTH>
+__device__ __forceinline__ void res_u_transform(const float* __restrict__ w, float* U_s) {
+  constexpr int USTR = C * C;
+  for (int e = threadIdx.x; e < C * C; e += NTH) {
+    const int co = e % C, ci = e / C;
+    float gk[3][3];
+#pragma unroll
+    for (int ky = 0; ky < 3; ++ky)
+#pragma unroll
+      for (int kx = 0; kx < 3; ++kx) gk[ky][kx] = w[((ky * 3 + kx) * C + ci) * C + co];
+    float t[4][3];
+#pragma unroll
+    for (int kx = 0; kx < 3; ++kx) {
+      t[0][kx] = gk[0][kx];
+      t[1][kx] = 0.5f * ((gk[0][kx] + gk[1][kx]) + gk[2][kx]);
+      t[2][kx] = 0.5f * ((gk[0][kx] - gk[1][kx]) + gk[2][kx]);
+      t[3][kx] = gk[2][kx];
+    }
+    const int b = ci >> 4, gq = (ci >> 2) & 3, v = ci & 3;
+#pragma unroll
+    for (int ra = 0; ra < 4; ++ra) {
+      const float u[4] = {t[ra][0], 0.5f * ((t[ra][0] + t[ra][1]) + t[ra][2]),
+                          0.5f * ((t[ra][0] - t[ra][1]) + t[ra][2]), t[ra][2]};
+#pragma unroll
+      for (int rb = 0; rb < 4; ++rb)
+        U_s[(4 * ra + rb) * USTR + ((b * 4 + gq) * C + co) * 4 + v] = u[rb];
+    }
+  }
+}
+
+// One (16 tiles x 16 output channels) task: Y[2 dy + dx] = A^T M A with
+// M[xi] = sum_ci U[xi][co][ci] (B^T d B)[xi][ci].  xp: the lane's 4x4 patch
+// (tile = lane & 15, channel quad = lane >> 4) in an LDS image of pixel pitch
+// C + 4; up: the lane's A fragments.  RELU: ReLU on the patch values.
+template <int C, bool RELU>
+__device__ __forceinline__ void res_tile(const float* xp, int rowstr, const float* up, f4 (&Y)[4]) {
+  constexpr int PP = C + 4, NB = C / 16, USTR = C * C;
+  f4 acc[16];
+#pragma unroll
+  for (int xi = 0; xi < 16; ++xi) acc[xi] = f4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int b = 0; b < NB; ++b) {
+    f4 d[16];
+#pragma unroll
+    for (int dy = 0; dy < 4; ++dy)
+#pragma unroll
+      for (int dx = 0; dx < 4; ++dx) {
+        f4 v = *reinterpret_cast<const f4*>(xp + dy * rowstr + dx * PP + 16 * b);
+        if constexpr (RELU) {
+#pragma unroll
+          for (int q = 0; q < 4; ++q) v[q] = relu0(v[q]);
+        }
+        d[4 * dy + dx] = v;
+      }
+    f4 s[16];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      s[q] = tsub(d[q], d[8 + q]);
+      s[4 + q] = tadd(d[4 + q], d[8 + q]);
+      s[8 + q] = tsub(d[8 + q], d[4 + q]);
+      s[12 + q] = tsub(d[4 + q], d[12 + q]);
+    }
+    f4 V[16];
+#pragma unroll
+    for (int ra = 0; ra < 4; ++ra) {
+      V[4 * ra + 0] = tsub(s[4 * ra + 0], s[4 * ra + 2]);
+      V[4 * ra + 1] = tadd(s[4 * ra + 1], s[4 * ra + 2]);
+      V[4 * ra + 2] = tsub(s[4 * ra + 2], s[4 * ra + 1]);
+      V[4 * ra + 3] = tsub(s[4 * ra + 1], s[4 * ra + 3]);
+    }
+    const float* ub = up + b * 4 * C * 4;
+#pragma unroll
+    for (int xp2 = 0; xp2 < 8; ++xp2) {
+      f4 ua[2];
+#pragma unroll
+      for (int q = 0; q < 2; ++q)
+        ua[q] = *reinterpret_cast<const f4*>(ub + (2 * xp2 + q) * USTR);
+#pragma unroll
+      for (int v = 0; v < 4; ++v)
+#pragma unroll
+        for (int q = 0; q < 2; ++q)
+          acc[2 * xp2 + q] = mfma4x<1>(ua[q][v], V[2 * xp2 + q][v], acc[2 * xp2 + q], v);
+    }
+  }
+  f4 tt[4][2];
+#pragma unroll
+  for (int ra = 0; ra < 4; ++ra) {
+    tt[ra][0] = tadd(tadd(acc[4 * ra], acc[4 * ra + 1]), acc[4 * ra + 2]);
+    tt[ra][1] = tsub(tsub(acc[4 * ra + 1], acc[4 * ra + 2]), acc[4 * ra + 3]);
+  }
+#pragma unroll
+  for (int c = 0; c < 2; ++c) {
+    Y[c] = tadd(tadd(tt[0][c], tt[1][c]), tt[2][c]);
+    Y[2 + c] = tsub(tsub(tt[1][c], tt[2][c]), tt[3][c]);
+  }
+}
+
+// LDS of one workgroup: U, the x rows and the t rows
+template <int C, int R>
+constexpr size_t res_block_bytes(int TX) {
+  return sizeof(float) * (16 * C * C + static_cast<size_t>(2 * R + 10) * (2 * TX + 2) * (C + 4));
+}
+
+template <int C, int R, int NW>
+__global__ __launch_bounds__(64 * NW) void wino_res_block_kernel(ResBlockArgs a) {
+  constexpr int NTH = 64 * NW, PP = C + 4, C4 = C / 4, LC4 = C4 == 4 ? 2 : 3, NS = C / 16;
+  constexpr int XR = R + 6, TR = R + 4;  // staged x rows / t rows
+  constexpr int KB = 4;                  // staging loads in flight per thread
+  static_assert(C == 16 || C == 32, "C");
+  static_assert(R % 2 == 0 && R >= 2, "band of whole tile rows");
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  const int Wl = 2 * a.TX + 2, rowstr = Wl * PP;
+  float* U_s = smem;                 // [16 xi][C/16][4 g][C][4]
+  float* x_s = smem + 16 * C * C;    // [XR][Wl][PP]: image row y0 - 3 + L, column c - 1
+  float* t_s = x_s + XR * rowstr;    // [TR][Wl][PP]: image row y0 - 2 + L, column c - 1
+
+  const int n = blockIdx.x / a.nbands, band = blockIdx.x - n * a.nbands;
+  const int y0 = band * R, ty0 = band * (R / 2);
+
+  // ---- stage the raw x rows (a buffer load past the end returns zeros: the
+  // padding needs no select), zero the t image, transform w1
+  const auto srcr = buf_rsrc(a.x, static_cast<int64_t>(a.N) * a.H * a.W * C);
+  const int nx = XR * Wl * C4;
+  for (int e0 = threadIdx.x; e0 < nx; e0 += KB * NTH) {
+    f4 stg[KB];
+#pragma unroll
+    for (int k = 0; k < KB; ++k) {
+      const int e = e0 + k * NTH;
+      const int ch = e & (C4 - 1), pix = e >> LC4;
+      const int L = fdivi(pix, a.rWl), col = pix - L * Wl;
+      const int y = y0 - 3 + L, xc = col - 1;
+      const bool in = e < nx && y >= 0 && y < a.H && xc >= 0 && xc < a.W;
+      stg[k] = bload(srcr, in ? static_cast<uint32_t>(((n * a.H + y) * a.W + xc) * C + 4 * ch) * 4u
+                              : kOOB);
+    }
+#pragma unroll
+    for (int k = 0; k < KB; ++k) {
+      const int e = e0 + k * NTH;
+      if (e < nx) *reinterpret_cast<f4*>(x_s + (e >> LC4) * PP + 4 * (e & (C4 - 1))) = stg[k];
+    }
+  }
+  for (int e = threadIdx.x; e < TR * rowstr / 4; e += NTH)
+    reinterpret_cast<f4*>(t_s)[e] = f4{0.f, 0.f, 0.f, 0.f};
+  res_u_transform<C, NTH>(a.w1, U_s);
+  __syncthreads();
+
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int g = lane >> 4, c16 = lane & 15;
+
+  // ---- conv1 over the t tile rows inside the image: local tile row tyl is
+  // tile row ty0 - 1 + tyl, its patch at x rows 2 tyl .., its outputs at t
+  // rows 2 tyl, 2 tyl + 1
+  {
+    const int lo = band == 0 ? 1 : 0;
+    const int hi = min(R / 2 + 1, a.TY - ty0);
+    const int nt = (hi - lo + 1) * a.TX, ng = (nt + 15) >> 4;
+    for (int task = wave; task < ng * NS; task += NW) {
+      const int sl = task / ng, grp = task - sl * ng;
+      const int co0 = 16 * sl;
+      int t = 16 * grp + c16;
+      const bool valid = t < nt;
+      if (!valid) t = 0;
+      const int tr = fdivi(t, a.rTX), tx = t - tr * a.TX;
+      const int tyl = lo + tr;
+      f4 Y[4];
+      res_tile<C, true>(x_s + (2 * tyl * Wl + 2 * tx) * PP + 4 * g, rowstr,
+                        U_s + (g * C + co0 + c16) * 4, Y);
+      const int co = co0 + 4 * g;
+      const f4 bv = *reinterpret_cast<const f4*>(a.b1 + co);
+#pragma unroll
+      for (int dy = 0; dy < 2; ++dy)
+#pragma unroll
+        for (int dx = 0; dx < 2; ++dx) {
+          const int oy = y0 - 2 + 2 * tyl + dy, ox = 2 * tx + dx;
+          if (!valid || oy < 0 || oy >= a.H || ox >= a.W) continue;  // t stays zero there
+          f4 v = Y[2 * dy + dx] + bv;
+#pragma unroll
+          for (int k = 0; k < 4; ++k) v[k] = relu0(v[k]);
+          *reinterpret_cast<f4*>(t_s + ((2 * tyl + dy) * Wl + ox + 1) * PP + co) = v;
+        }
+    }
+  }
+  __syncthreads();  // t complete, every wave done with w1's U
+  res_u_transform<C, NTH>(a.w2, U_s);
+  __syncthreads();
+
+  // ---- conv2 over the band's tile rows: local tile row tyl is tile row
+  // ty0 + tyl, its patch at t rows 2 tyl + 1 ..
+  {
+    const int nt = min(R / 2, a.TY - ty0) * a.TX, ng = (nt + 15) >> 4;
+    for (int task = wave; task < ng * NS; task += NW) {
+      const int sl = task / ng, grp = task - sl * ng;
+      const int co0 = 16 * sl;
+      int t = 16 * grp + c16;
+      const bool valid = t < nt;
+      if (!valid) t = 0;
+      const int tyl = fdivi(t, a.rTX), tx = t - tyl * a.TX;
+      f4 Y[4];
+      res_tile<C, false>(t_s + ((2 * tyl + 1) * Wl + 2 * tx) * PP + 4 * g, rowstr,
+                         U_s + (g * C + co0 + c16) * 4, Y);
+      const int co = co0 + 4 * g;
+      const f4 bv = *reinterpret_cast<const f4*>(a.b2 + co);
+#pragma unroll
+      for (int dy = 0; dy < 2; ++dy)
+#pragma unroll
+        for (int dx = 0; dx < 2; ++dx) {
+          const int ly = 2 * tyl + dy, ox = 2 * tx + dx;
+          const int oy = y0 + ly;
+          if (!valid || oy >= a.H || ox >= a.W) continue;
+          f4 v = Y[2 * dy + dx] + bv;
+          v += *reinterpret_cast<const f4*>(x_s + ((ly + 3) * Wl + ox + 1) * PP + co);
+          if (a.last) {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) v[k] = relu0(v[k]);
+          }
+          const int64_t o = ((static_cast<int64_t>(n) * a.H + oy) * a.W + ox) * C + co;
+          *reinterpret_cast<f4*>(a.y + o) = v;
+        }
+    }
+  }
+}
+
+template <int C, int R, int NW>
+bool run_res_block(const ResBlockArgs& a, hipStream_t s) {
+  const size_t bytes = res_block_bytes<C, R>(a.TX);
+  if (bytes > 160 * 1024) return false;
+  ResBlockArgs b = a;
+  b.nbands = (a.H + R - 1) / R;
+  auto kern = wino_res_block_kernel<C, R, NW>;
+  allow_lds_w(kern, bytes);
+  hipLaunchKernelGGL(kern, dim3(a.N * b.nbands), dim3(64 * NW), bytes, s, b);
+  return true;
+}
+
 }  // namespace
+
+// Band heights (output rows per workgroup) of the fused residual block: per
+// channel count the taller instance where its LDS fits the map's width, else
+// the shorter one.  C = 16: 12 rows (36x48: 3 bands of 152 KB, 42x42: 4
+// bands), 8 rows (36x64: 5 bands); C = 32, where U alone is 64 KB: 6 rows
+// (18x24 and 21x21: 3 / 4 bands, 9x12 and 11x11: 2), 4 rows (18x32: 5 bands,
+// 9x16: 3).  76-150 images then launch 150-750 workgroups of one per CU.
+int wino_res_block_band(int C, int W) {
+  const int TX = (W + 1) / 2;
+  if (C == 16) {
+    if (res_block_bytes<16, 12>(TX) <= 160 * 1024) return 12;
+    if (res_block_bytes<16, 8>(TX) <= 160 * 1024) return 8;
+  } else if (C == 32) {
+    if (res_block_bytes<32, 6>(TX) <= 160 * 1024) return 6;
+    if (res_block_bytes<32, 4>(TX) <= 160 * 1024) return 4;
+  }
+  return 0;
+}
+
+bool wino_res_block_launch(const float* x, const float* w1, const float* b1, const float* w2,
+                           const float* b2, float* y, int N, int H, int W, int C, bool last,
+                           hipStream_t s) {
+  if (N < 1 || N > kResBlockMaxFrames || !wino_enabled()) return false;
+  const int R = wino_res_block_band(C, W);
+  if (R == 0) return false;
+  // the two launches this replaces must both run the Winograd forward (the
+  // direct kernel they would fall to sums in another order)
+  ConvArgs c{};
+  c.src = x; c.w = w1; c.bias = b1; c.out = y;
+  c.N = N; c.Hs = H; c.Ws = W; c.Cs = C;
+  c.Ho = H; c.Wo = W; c.Cout = C;
+  c.pt = 1; c.pl = 1; c.D = 1;
+  c.wcin = C; c.wcout = C;
+  c.relu_in = 1; c.relu_out = 1;
+  t_wino_probe = true;
+  bool both = wino_conv_launch(c, false, s);
+  c.w = w2; c.bias = b2; c.add = x;
+  c.relu_in = 0; c.relu_out = last ? 1 : 0;
+  both = both && wino_conv_launch(c, false, s);
+  t_wino_probe = false;
+  if (!both) return false;
+  ResBlockArgs a{};
+  a.x = x; a.w1 = w1; a.b1 = b1; a.w2 = w2; a.b2 = b2; a.y = y;
+  a.N = N; a.H = H; a.W = W;
+  a.TY = (H + 1) / 2; a.TX = (W + 1) / 2;
+  a.last = last ? 1 : 0;
+  a.rTX = 1.f / static_cast<float>(a.TX);
+  a.rWl = 1.f / static_cast<float>(2 * a.TX + 2);
+  if (C == 16) {
+    if (R == 12) return run_res_block<16, 12, 12>(a, s);
+    return run_res_block<16, 8, 12>(a, s);
+  }
+  if (R == 6) return run_res_block<32, 6, 8>(a, s);
+  return run_res_block<32, 4, 8>(a, s);
+}
 
 int conv_wino_fault(int v) {
   const int old = g_wino_fault;

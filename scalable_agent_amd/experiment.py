@@ -153,7 +153,26 @@ def _make_agent(flags, num_actions, frame_shape, device, seed, dtype=None):
                seed=seed, backend=backend, compute_dtype=cdt,
                num_value_heads=num_value_heads(flags),
                pipeline_chunks=getattr(flags, 'pipeline_chunks', 1),
-               actor_core=getattr(flags, 'actor_core', 'ops'))
+               actor_core=getattr(flags, 'actor_core', 'ops'),
+               torso_blocks=getattr(flags, 'torso_blocks', 'ops'))
+
+
+def _log_torso_blocks(flags, model):
+  """Which form the inference model's residual blocks run (--torso_blocks)."""
+  asked = getattr(flags, 'torso_blocks', 'ops')
+  used = model.torso_blocks
+  if asked == used:
+    log.info('actor inference torso blocks: %s', used)
+    return
+  agent = model.agent
+  if getattr(agent, 'backend', 'torch') != 'hip' or model.device.type != 'cuda':
+    why = 'the torch backend has no block kernel'
+  elif agent.torso_kind != 'deep':
+    why = 'the %s torso has no residual blocks' % agent.torso_kind
+  else:
+    why = 'bf16 inference already runs one kernel per block'
+  log.info('actor inference torso blocks: %s (--torso_blocks=%s does not '
+           'apply: %s)', used, asked, why)
 
 
 def _log_actor_core(flags, model):
@@ -601,6 +620,7 @@ def train(flags):
             seed=flags.seed + 17 * rank + 7919 * lane)
         if lane == 0:
           _log_actor_core(flags, lane_model)
+          _log_torso_blocks(flags, lane_model)
         servers.append(BoardServer(lane_model, lane_board,
                                    gather_us=flags.inference_gather_us,
                                    depth=flags.inference_board_depth))
@@ -623,6 +643,7 @@ def train(flags):
     model = inference_lib.InferenceModel(inf_agent, inf_device, use_instr,
                                          seed=flags.seed + 17 * rank)
     _log_actor_core(flags, model)
+    _log_torso_blocks(flags, model)
     model.publish(learner.flat.params)
     infer = inference_lib.make_batched_infer(
         model, flags.inference_min_batch, flags.inference_max_batch,

@@ -133,6 +133,14 @@ class InferenceModel(object):
     return ('fused' if fused is not None and
             fused(self._gen, self.device.type == 'cuda') else 'ops')
 
+  @property
+  def torso_blocks(self):
+    """'fused' when this model's torso runs each residual block as one
+    kernel (Agent(torso_blocks='fused') where it applies), else 'ops'."""
+    fused = getattr(self.agent, 'torso_blocks_fused', None)
+    return ('fused' if fused is not None and
+            fused(self.device.type == 'cuda') else 'ops')
+
   @torch.no_grad()
   def step_device(self, last_action, reward, done, frame, instr_ids,
                   instr_len, c, h, has_instr, epilogue=None):

@@ -122,8 +122,16 @@ class Agent(nn.Module):
 
   def __init__(self, num_actions, torso='shallow', frame_shape=(72, 96, 3),
                seed=None, backend='torch', compute_dtype=torch.float32,
-               num_value_heads=1, pipeline_chunks=1, actor_core='ops'):
+               num_value_heads=1, pipeline_chunks=1, actor_core='ops',
+               torso_blocks='ops'):
     super().__init__()
+    # 'fused': a no-grad forward of the fp32 HIP deep torso on a board's
+    # worth of frames runs each residual block as ONE kernel
+    # (ops/conv_f32.py _DeepTorsoF32Infer) where it applies
+    # (torso_blocks_fused); 'ops': two Winograd convs per block
+    if torso_blocks not in ('ops', 'fused'):
+      raise ValueError('unknown torso_blocks %r' % (torso_blocks,))
+    self.torso_blocks = torso_blocks
     # 'fused': the T = 1 inference step after the torso-FC GEMM is ONE kernel
     # (ops/actor_core.py) where it applies (actor_core_fused); 'ops': the
     # x-projection, LSTM step and heads + sampler ops
@@ -521,6 +529,14 @@ class Agent(nn.Module):
             self.compute_dtype == torch.float32 and self.fused_core_ready() and
             self.num_actions <= ACTOR_MAX_ACTIONS and
             isinstance(generator, PhiloxStream))
+
+  def torso_blocks_fused(self, cuda=True):
+    """True when `torso_blocks='fused'` is honoured for a no-grad forward of
+    CUDA frames: HIP backend, deep torso, and the exact-fp32 torso kernels
+    run it (the bf16 torso fuses its blocks on its own; the shallow torso has
+    none).  Otherwise the torso runs as with 'ops'."""
+    return (self.torso_blocks == 'fused' and self.backend == 'hip' and cuda and
+            self.torso_kind == 'deep' and not _bf16_torso_ready(self))
 
   def _fused_step(self, actions, env_outputs, core_state, generator, epilogue):
     """The T = 1 actor step with the fused core: torso, the torso-FC GEMM

@@ -130,61 +130,7 @@ class _DeepTorsoF32(torch.autograd.Function):
 
   @staticmethod
   def forward(ctx, frames, *params):
-    C = ext()
-    # stage 0 reads a 4-channel fp32 x / 255 image (one 16-B load per pixel
-    # in the conv+pool and scatter-wgrad stagers), or the uint8 frames
-    x = frames.contiguous()
-    if not U8_DIRECT['deep']:
-      x = C.cf32_frames_f32(x)
-    saved, meta = [], []
-    p = 0
-    for s in range(3):
-      w, b = params[p], params[p + 1]
-      p += 2
-      if s == 0 and w.shape[2] != x.shape[3]:
-        w = _pad_cin(w, x.shape[3])  # zero rows for the image's pad channel
-      H, W = x.shape[1], x.shape[2]
-      pbh = layers.same_pads(H, 3, 2)[0]
-      pbw = layers.same_pads(W, 3, 2)[0]
-      fused = (C.cf32_wino_conv_pool_fwd(x, w, b) if x.dtype == torch.float32
-               else [])
-      if fused:
-        # stage 0 (4-channel image -> 16) and stage 1 (16 -> 32) heads
-        # with the pool in the Winograd epilogue (the pre-pool map only in
-        # LDS); other shapes: the direct conv+pool or conv + maxpool_fwd
-        xa, arg = fused
-      elif s in FUSED_POOL_STAGES:
-        xa, arg = C.cf32_conv_pool_fwd(x, w, b, pbh, pbw)
-      else:
-        conv = C.cf32_conv_fwd(x, w, b, 1, 1, 1, H, W)
-        xa, arg = C.cf32_maxpool_fwd(conv, pbh, pbw)
-        del conv
-      h, w_ = xa.shape[1], xa.shape[2]
-      # stage 0 on the scatter wgrad path: its backward reads the uint8
-      # frames, so the fp32 image is not kept alive for it
-      keep = (frames if (s == 0 and PW_U8 and POOL_SCATTER and
-                         x.dtype == torch.float32 and frames.dtype == torch.uint8 and
-                         frames.shape[3] <= 4 and xa.shape[3] == 16)
-              else x)
-      saved += [keep, arg]
-      for blk in range(2):
-        w1, b1, w2, b2 = params[p:p + 4]
-        p += 4
-        last = s == 2 and blk == 1
-        # t stored ReLU'd: conv 2 reads it as is, its mask is (t > 0)
-        t = C.cf32_conv_fwd(xa, w1, b1, 1, 1, 1, h, w_, relu_in=True,
-                            relu_out=True)
-        y = C.cf32_conv_fwd(t, w2, b2, 1, 1, 1, h, w_, add=xa, relu_out=last)
-        saved += [xa, t]
-        xa = y
-      meta.append((H, W, h, w_, pbh, pbw))
-      x = xa
-    ctx.save_for_backward(*saved, x, *params)
-    ctx.meta = meta
-    ctx.nparams = len(params)
-    if DEBUG_TAPE is not None:
-      DEBUG_TAPE['saved'] = [t.clone() for t in saved]
-    return x.reshape(x.shape[0], -1)
+    return _deep_forward(ctx, frames, params)
 
   @staticmethod
   def backward(ctx, grad_out):
@@ -213,6 +159,86 @@ class _DeepTorsoF32(torch.autograd.Function):
       C.cf32_wgrad_defer(False)
       C.cf32_wgrad_flush()
     return (None,) + grad_sink.returned(gv, direct)
+
+
+class _DeepTorsoF32Infer(_DeepTorsoF32):
+  """Small no-grad batches (actor inference, Agent(torso_blocks='fused')):
+  each residual block is one launch, nothing is kept for a backward."""
+
+  @staticmethod
+  def forward(ctx, frames, *params):
+    return _deep_forward(None, frames, params)
+
+  @staticmethod
+  def backward(ctx, grad_out):
+    raise RuntimeError('the inference torso has no backward')
+
+
+def _deep_forward(ctx, frames, params):
+  """Forward of the deep torso.  ctx None (_DeepTorsoF32Infer): residual
+  blocks run cf32_res_block_fwd (both convs in one launch, t only in LDS,
+  bitwise the two launches) where that kernel takes the shape."""
+  C = ext()
+  fused_blocks = ctx is None
+  # stage 0 reads a 4-channel fp32 x / 255 image (one 16-B load per pixel
+  # in the conv+pool and scatter-wgrad stagers), or the uint8 frames
+  x = frames.contiguous()
+  if not U8_DIRECT['deep']:
+    x = C.cf32_frames_f32(x)
+  saved, meta = [], []
+  p = 0
+  for s in range(3):
+    w, b = params[p], params[p + 1]
+    p += 2
+    if s == 0 and w.shape[2] != x.shape[3]:
+      w = _pad_cin(w, x.shape[3])  # zero rows for the image's pad channel
+    H, W = x.shape[1], x.shape[2]
+    pbh = layers.same_pads(H, 3, 2)[0]
+    pbw = layers.same_pads(W, 3, 2)[0]
+    fused = (C.cf32_wino_conv_pool_fwd(x, w, b) if x.dtype == torch.float32
+             else [])
+    if fused:
+      # stage 0 (4-channel image -> 16) and stage 1 (16 -> 32) heads
+      # with the pool in the Winograd epilogue (the pre-pool map only in
+      # LDS); other shapes: the direct conv+pool or conv + maxpool_fwd
+      xa, arg = fused
+    elif s in FUSED_POOL_STAGES:
+      xa, arg = C.cf32_conv_pool_fwd(x, w, b, pbh, pbw)
+    else:
+      conv = C.cf32_conv_fwd(x, w, b, 1, 1, 1, H, W)
+      xa, arg = C.cf32_maxpool_fwd(conv, pbh, pbw)
+      del conv
+    h, w_ = xa.shape[1], xa.shape[2]
+    # stage 0 on the scatter wgrad path: its backward reads the uint8
+    # frames, so the fp32 image is not kept alive for it
+    keep = (frames if (s == 0 and PW_U8 and POOL_SCATTER and
+                       x.dtype == torch.float32 and frames.dtype == torch.uint8 and
+                       frames.shape[3] <= 4 and xa.shape[3] == 16)
+            else x)
+    saved += [keep, arg]
+    for blk in range(2):
+      w1, b1, w2, b2 = params[p:p + 4]
+      p += 4
+      last = s == 2 and blk == 1
+      y = C.cf32_res_block_fwd(xa, w1, b1, w2, b2, last) if fused_blocks else []
+      if y:
+        xa = y[0]
+        continue
+      # t stored ReLU'd: conv 2 reads it as is, its mask is (t > 0)
+      t = C.cf32_conv_fwd(xa, w1, b1, 1, 1, 1, h, w_, relu_in=True,
+                          relu_out=True)
+      y = C.cf32_conv_fwd(t, w2, b2, 1, 1, 1, h, w_, add=xa, relu_out=last)
+      saved += [xa, t]
+      xa = y
+    meta.append((H, W, h, w_, pbh, pbw))
+    x = xa
+  if ctx is not None:
+    ctx.save_for_backward(*saved, x, *params)
+    ctx.meta = meta
+    ctx.nparams = len(params)
+    if DEBUG_TAPE is not None:
+      DEBUG_TAPE['saved'] = [t.clone() for t in saved]
+  return x.reshape(x.shape[0], -1)
 
 
 def _deep_backward(C, ctx, saved, params, gv, dy):
@@ -334,7 +360,15 @@ def torso_forward_f32(agent, frames):
     # an inference agent's stage-0 weights, zero-padded to the image's 4
     # channels once per weight publish (no concatenation kernel per step)
     params = [cache['w0pad']] + params[1:]
-  return _chunked(_DeepTorsoF32, frames, params)
+  from .conv import FUSED_BLOCK_MAX_FRAMES
+  # actor inference (no autograd, a board's worth of frames) of an agent
+  # built with torso_blocks='fused': one launch per residual block
+  fn = (_DeepTorsoF32Infer
+        if (getattr(agent, 'torso_blocks', 'ops') == 'fused' and
+            not torch.is_grad_enabled() and
+            frames.shape[0] <= FUSED_BLOCK_MAX_FRAMES)
+        else _DeepTorsoF32)
+  return _chunked(fn, frames, params)
 
 
 def linear_relu_f32(x, w, b):

@@ -97,9 +97,55 @@ if not ONLY or ONLY in 'head conv2 pool deep':
   flop = 2.0 * N * 36 * 48 * 9 * 16 * 32
   print('%-26s fwd+pool: conv + maxpool %8.1f us | fused %8.1f us %6.1f TF' % (
       'head conv2 16->32 36x48', tc, tfp, flop / tfp / 1e6), flush=True)
+
+
+def timeit_graph(fn, inner=20):
+  """us per call of fn inside a captured graph of `inner` back-to-back calls
+  (actor inference replays graphs: no host launch cost between kernels)."""
+  side = torch.cuda.Stream()
+  side.wait_stream(torch.cuda.current_stream())
+  with torch.cuda.stream(side):
+    fn()
+    side.synchronize()
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g, stream=side):
+      for _ in range(inner):
+        fn()
+    g.replay()
+    side.synchronize()
+    s, e = torch.cuda.Event(True), torch.cuda.Event(True)
+    s.record(side)
+    for _ in range(REPS):
+      g.replay()
+    e.record(side)
+    side.synchronize()
+  return s.elapsed_time(e) / (REPS * inner) * 1e3
+
+
+# residual block forward at an actor-inference batch (N <= 512, e.g. 76 or
+# 150): the two Winograd convs vs the one-launch block (wino_res_block_kernel),
+# eager and inside a captured graph
+if (not ONLY or ONLY in 'block') and N <= 512:
+  for name, H, W, Cc in [('res16 36x48', 36, 48, 16), ('res32 18x24', 18, 24, 32),
+                         ('res32 9x12', 9, 12, 32)]:
+    x = torch.randn(N, H, W, Cc, device=dev)
+    w1 = torch.randn(3, 3, Cc, Cc, device=dev) * 0.1
+    w2 = torch.randn(3, 3, Cc, Cc, device=dev) * 0.1
+    b1 = torch.randn(Cc, device=dev)
+    b2 = torch.randn(Cc, device=dev)
+    conv1 = lambda: C.cf32_conv_fwd(x, w1, b1, 1, 1, 1, H, W, relu_in=True, relu_out=True)
+    t = conv1()
+    conv2 = lambda: C.cf32_conv_fwd(t, w2, b2, 1, 1, 1, H, W, add=x)
+    block = lambda: C.cf32_res_block_fwd(x, w1, b1, w2, b2, False)
+    assert block(), 'the fused block declined %s' % name
+    for label, tm in (('eager', timeit), ('graph', timeit_graph)):
+      t1, t2, tb = tm(conv1), tm(conv2), tm(block)
+      print('%-14s N=%-4d %s block fwd: conv1 %6.1f + conv2 %6.1f = %6.1f us | fused '
+            '%6.1f us (band %d rows)' % (name, N, label, t1, t2, t1 + t2, tb,
+                                        C.cf32_res_block_band(Cc, W)), flush=True)
 if ONLY:
   sys.exit(0)
-xp = torch.randn(N, 72, 96, 16, device=dev)
+xp =torch.randn(N, 72, 96, 16, device=dev)
 tp = timeit(lambda: C.cf32_maxpool_fwd(xp, 0, 0))
 y, arg = C.cf32_maxpool_fwd(xp, 0, 0)
 tb = timeit(lambda: C.cf32_maxpool_bwd(y, arg, 72, 96, 0, 0))
