@@ -31,8 +31,17 @@
 // register prefetch issued one range ahead, and its waves take (16-tile
 // group, output-channel slice) tasks.  Every range but the batch's last is
 // full, so the waves stay balanced for any image size.
+//
+// The device utilities and one set of phase functions (weight, input and
+// output transforms, the MFMA block, the register-prefetch stager) are in
+// wino_core.h.  The stage-head kernels and the residual block are built from
+// them alone; wino_conv_kernel calls them for the weight transform, the
+// stager and the input / output transforms, the two fused backward kernels
+// for the weight transform and the slot tables; each kernel that keeps text
+// of its own says why.
 #include "conv_f32.h"
 #include "knobs.h"
+#include "wino_core.h"
 
 #include <algorithm>
 #include <cstdlib>
@@ -41,74 +50,11 @@ namespace sa {
 namespace cf32 {
 namespace {
 
-typedef float f4 __attribute__((ext_vector_type(4)));
+using namespace wino;  // the shared phase functions and device utilities (wino_core.h)
+
 typedef __attribute__((address_space(1))) unsigned gu32;
 
 constexpr int kMaxParts = 4;  // images one range may touch
-
-// Measurement knobs (SA_WINO_ABLATE / SA_FUSED_ABLATE: drop parts of a
-// kernel's work to time the rest) exist only in builds with
-// -DSA_MEASURE_KNOBS=1; in production builds every knob test folds to false,
-// so no environment variable can remove a synchronisation or a store.
-#ifndef SA_MEASURE_KNOBS
-#define SA_MEASURE_KNOBS 0
-#endif
-__device__ __forceinline__ bool knob(int v, int bit) {
-  return SA_MEASURE_KNOBS && (v & bit) != 0;
-}
-
-__device__ __forceinline__ f4 mfma4(float a, float b, f4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
-}
-
-// Pricing builds only (-DSA_WINO_XMFMA=bits, never a production build): the
-// MFMA at an odd (compile-time, unrolled) index becomes ONE VALU FMA on the
-// same operands - half the matrix work, wrong results, everything else
-// unchanged - to measure how much of a kernel the matrix pipe sets.  Bit 0:
-// forward / data-gradient MFMAs, bit 1: weight-gradient MFMAs.
-#ifndef SA_WINO_XMFMA
-#define SA_WINO_XMFMA 0
-#endif
-template <int BIT>
-__device__ __forceinline__ f4 mfma4x(float a, float b, f4 c, int idx) {
-  if ((SA_WINO_XMFMA & BIT) && (idx & 1)) {
-    c[0] = fmaf(a, b, c[0]);
-    return c;
-  }
-  return mfma4(a, b, c);
-}
-
-// 16-B loads through a buffer descriptor: an offset at or past the buffer's
-// end returns zeros (the hardware range check), so a stager's padding and
-// out-of-image elements need no select when they are committed to LDS, and
-// the per-lane address is a 32-bit byte offset.  Launchers refuse tensors
-// of >= 4 GB.
-constexpr uint32_t kOOB = 0xFFFFFFF0u;
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t buf_rsrc(const float* p, int64_t floats) {
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p), 0,
-                                           static_cast<int>(static_cast<uint32_t>(floats * 4)),
-                                           0x00020000);
-}
-__device__ __forceinline__ f4 bload(__amdgpu_buffer_rsrc_t r, uint32_t byte_off) {
-  return __builtin_bit_cast(f4, __builtin_amdgcn_raw_buffer_load_b128(r, byte_off, 0, 0));
-}
-constexpr int64_t kMaxBufBytes = 0xFFFFFF00ll;
-
-// Winograd transform add / subtract on float4 channel quads.  (A packed
-// v_pk_add_f32 form was measured in round 4 and removed: the backend keeps
-// <2 x float> arithmetic scalar, an inline-asm form read MFMA accumulators
-// without the required wait states, and packed f32 beside MFMAs is an
-// anti-lever on gfx950.)
-__device__ __forceinline__ f4 tadd(f4 a, f4 b) { return a + b; }
-__device__ __forceinline__ f4 tsub(f4 a, f4 b) { return a - b; }
-
-// ReLU as one integer max on the bit pattern (negative floats, -0 and
-// negative NaNs have the sign bit set: signed-int max with 0 gives +0);
-// fmaxf(x, 0) is two instructions under IEEE mode (a canonicalising
-// v_max_f32 x, x first)
-__device__ __forceinline__ float relu0(float x) {
-  return __int_as_float(max(__float_as_int(x), 0));
-}
 
 // Weight-gradient k-step: lane group g reads tile 4 st + kperm(g), order
 // {0, 2, 1, 3}.  Adjacent tiles sit 2 pixels apart in LDS (8 banks for a
@@ -329,6 +275,8 @@ struct TileGeo {
 // FL: compile-time epilogue / stager flags (bit 0 ReLU on the input, 1 ReLU
 // on the output, 2 mask, 3 residual add, 4 bias), or -1 = read them from
 // the arguments (a runtime ReLU is a max + select per staged value)
+// (The MFMA block keeps its own text: on wino_mfma_block the 16 -> 32
+// forward measured 4 % slower, profiles/experiments.md.)
 template <int CIN, int COUT, int NH, int NW, int RT, int MAXC, int WPS, int FL = -1, int GH = 0,
           int GW = 0>
 __global__ __launch_bounds__(64 * NW, WPS) void wino_conv_kernel(WinoArgs a) {
@@ -356,13 +304,8 @@ __global__ __launch_bounds__(64 * NW, WPS) void wino_conv_kernel(WinoArgs a) {
 
   // ---- weight transform U = G g G^T into LDS (once per workgroup; the
   // measurement bit 16 skips it to time the rest)
-  for (int e = threadIdx.x; e < (knob(a.ablate, 16) ? 0 : CIN * COUT); e += NTH) {
-    const int co = e % COUT, ci = e / COUT;
-    float gk[3][3];
-#pragma unroll
-    for (int ky = 0; ky < 3; ++ky)
-#pragma unroll
-      for (int kx = 0; kx < 3; ++kx) {
+  wino_u_to_lds<NB, COUT, NTH>(
+      U_s, knob(a.ablate, 16) ? 0 : CIN * COUT, [&](int ky, int kx, int ci, int co) {
         float v = 0.f;
         if (!a.flip) {
           if (ci < a.wcin && co < a.wcout)
@@ -373,26 +316,8 @@ __global__ __launch_bounds__(64 * NW, WPS) void wino_conv_kernel(WinoArgs a) {
           if (co < a.wcin && ci < a.wcout)
             v = a.w[(((2 - ky) * 3 + (2 - kx)) * a.wcin + co) * a.wcout + ci];
         }
-        gk[ky][kx] = v;
-      }
-    float t[4][3];
-#pragma unroll
-    for (int kx = 0; kx < 3; ++kx) {
-      t[0][kx] = gk[0][kx];
-      t[1][kx] = 0.5f * ((gk[0][kx] + gk[1][kx]) + gk[2][kx]);
-      t[2][kx] = 0.5f * ((gk[0][kx] - gk[1][kx]) + gk[2][kx]);
-      t[3][kx] = gk[2][kx];
-    }
-    const int b = ci >> 4, gq = (ci >> 2) & 3, v = ci & 3;
-#pragma unroll
-    for (int ra = 0; ra < 4; ++ra) {
-      const float u[4] = {t[ra][0], 0.5f * ((t[ra][0] + t[ra][1]) + t[ra][2]),
-                          0.5f * ((t[ra][0] - t[ra][1]) + t[ra][2]), t[ra][2]};
-#pragma unroll
-      for (int rb = 0; rb < 4; ++rb)
-        U_s[(4 * ra + rb) * USTR + ((b * 4 + gq) * COUT + co) * 4 + v] = u[rb];
-    }
-  }
+        return v;
+      });
 
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int g = lane >> 4, c16 = lane & 15;
@@ -414,17 +339,8 @@ __global__ __launch_bounds__(64 * NW, WPS) void wino_conv_kernel(WinoArgs a) {
   // applied too): a branch or a use right after a load makes the compiler
   // wait for it, serialising the prefetch.
   int* tab_s = reinterpret_cast<int*>(x_s + G.maxrows * Wl * PP);  // [maxrows]
-  static_assert(MAXC <= 32, "stager mask");
   int sl_L[MAXC], sl_x[MAXC];
-#pragma unroll
-  for (int k = 0; k < MAXC; ++k) {
-    const int e = threadIdx.x + k * NTH;
-    const int ch = e & (C4 - 1), pix = e >> LC4;
-    const int L = pix / G.WL0, col = pix - L * G.WL0;
-    sl_L[k] = L < G.maxrows ? L : -1;
-    // -1: column in the zero padding
-    sl_x[k] = (col >= 1 && col <= G.W) ? (col - 1) * CIN + 4 * ch : -1;
-  }
+  wino_slots<MAXC, NTH, CIN>(G.WL0, G.maxrows, G.W, sl_L, sl_x);
   auto build_tab = [&](int rr) {
     const RangeGeom gm = G.range(rr);
     const int L = threadIdx.x;
@@ -442,12 +358,7 @@ __global__ __launch_bounds__(64 * NW, WPS) void wino_conv_kernel(WinoArgs a) {
   f4 stg[MAXC];
   const auto srcr = buf_rsrc(a.src, static_cast<int64_t>(a.N) * G.H * G.W * CIN);
   auto prefetch = [&]() __attribute__((always_inline)) {  // reads tab_s
-#pragma unroll
-    for (int k = 0; k < MAXC; ++k) {
-      const int rb = sl_L[k] >= 0 ? tab_s[sl_L[k]] : -1;
-      const bool in = rb >= 0 && sl_x[k] >= 0 && !knob(a.ablate, 2);
-      stg[k] = bload(srcr, in ? static_cast<uint32_t>(rb + sl_x[k]) * 4u : kOOB);
-    }
+    wino_prefetch(srcr, tab_s, sl_L, sl_x, knob(a.ablate, 2), stg);
   };
   build_tab(r);
   __syncthreads();
@@ -523,29 +434,8 @@ __global__ __launch_bounds__(64 * NW, WPS) void wino_conv_kernel(WinoArgs a) {
 #pragma unroll
       for (int b = 0; b < NB; ++b) {
         // the lane's 4x4 input patch, 4 channels, and V = B^T d B
-        f4 d[16];
-#pragma unroll
-        for (int dy = 0; dy < 4; ++dy)
-#pragma unroll
-          for (int dx = 0; dx < 4; ++dx)
-            d[4 * dy + dx] =
-                *reinterpret_cast<const f4*>(xp + dy * rowstr + dx * PP + 16 * b);
-        f4 s[16];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          s[q] = tsub(d[q], d[8 + q]);
-          s[4 + q] = tadd(d[4 + q], d[8 + q]);
-          s[8 + q] = tsub(d[8 + q], d[4 + q]);
-          s[12 + q] = tsub(d[4 + q], d[12 + q]);
-        }
-        f4 V[16];
-#pragma unroll
-        for (int ra = 0; ra < 4; ++ra) {
-          V[4 * ra + 0] = tsub(s[4 * ra + 0], s[4 * ra + 2]);
-          V[4 * ra + 1] = tadd(s[4 * ra + 1], s[4 * ra + 2]);
-          V[4 * ra + 2] = tsub(s[4 * ra + 2], s[4 * ra + 1]);
-          V[4 * ra + 3] = tsub(s[4 * ra + 1], s[4 * ra + 3]);
-        }
+        const F16 Vs = wino_input_transform(wino_load_patch(xp + 16 * b, rowstr, PP));
+        const f4 (&V)[16] = Vs.v;
         // 16 xi x 4 k-steps x NH slices; two xi chains interleaved (the
         // 16x16x4 f32 MFMA's dependent latency is 40 cycles, issue 32)
         const float* ub = up + b * 4 * COUT * 4;
@@ -575,18 +465,8 @@ __global__ __launch_bounds__(64 * NW, WPS) void wino_conv_kernel(WinoArgs a) {
         const int co = co0 + 16 * h + 4 * g;
         f4 bv = {0.f, 0.f, 0.f, 0.f};
         if (f_bias) bv = *reinterpret_cast<const f4*>(a.bias + co);
-        f4 tt[4][2];
-#pragma unroll
-        for (int ra = 0; ra < 4; ++ra) {
-          tt[ra][0] = tadd(tadd(acc[h][4 * ra], acc[h][4 * ra + 1]), acc[h][4 * ra + 2]);
-          tt[ra][1] = tsub(tsub(acc[h][4 * ra + 1], acc[h][4 * ra + 2]), acc[h][4 * ra + 3]);
-        }
-        f4 Y[4];
-#pragma unroll
-        for (int c = 0; c < 2; ++c) {
-          Y[c] = tadd(tadd(tt[0][c], tt[1][c]), tt[2][c]);
-          Y[2 + c] = tsub(tsub(tt[1][c], tt[2][c]), tt[3][c]);
-        }
+        const F4x4 Ys = wino_output_transform(acc[h]);
+        const f4 (&Y)[4] = Ys.v;
 #pragma unroll
         for (int dy = 0; dy < 2; ++dy)
 #pragma unroll
@@ -932,33 +812,23 @@ __global__ __launch_bounds__((64 * PoolGeo<CIN, COUT, RT>::NW), 3) void wino_con
   int* tab_s = reinterpret_cast<int*>(x_s + P::XREG);  // [6]
 
   // U = G g G^T (forward weights HWIO [3][3][CIN][COUT])
-  for (int e = threadIdx.x; e < CIN * COUT; e += NTH) {
-    const int co = e % COUT, ci = e / COUT;
-    float gk[3][3];
+  auto wtap = [&](int ky, int kx, int ci, int co) {
+    return a.w[((ky * 3 + kx) * CIN + ci) * COUT + co];
+  };
+  if constexpr (CIN == 16) {
+    wino_u_to_lds<1, COUT, NTH>(U_s, CIN * COUT, wtap);
+  } else {
+    for (int e = threadIdx.x; e < CIN * COUT; e += NTH) {
+      const int co = e % COUT, ci = e / COUT;
+      float gk[3][3];
 #pragma unroll
-    for (int ky = 0; ky < 3; ++ky)
+      for (int ky = 0; ky < 3; ++ky)
 #pragma unroll
-      for (int kx = 0; kx < 3; ++kx) gk[ky][kx] = a.w[((ky * 3 + kx) * CIN + ci) * COUT + co];
-    float t[4][3];
+        for (int kx = 0; kx < 3; ++kx) gk[ky][kx] = wtap(ky, kx, ci, co);
+      float u[16];
+      wino_weight_transform(gk, u);
 #pragma unroll
-    for (int kx = 0; kx < 3; ++kx) {
-      t[0][kx] = gk[0][kx];
-      t[1][kx] = 0.5f * ((gk[0][kx] + gk[1][kx]) + gk[2][kx]);
-      t[2][kx] = 0.5f * ((gk[0][kx] - gk[1][kx]) + gk[2][kx]);
-      t[3][kx] = gk[2][kx];
-    }
-#pragma unroll
-    for (int ra = 0; ra < 4; ++ra) {
-      const float u[4] = {t[ra][0], 0.5f * ((t[ra][0] + t[ra][1]) + t[ra][2]),
-                          0.5f * ((t[ra][0] - t[ra][1]) + t[ra][2]), t[ra][2]};
-#pragma unroll
-      for (int rb = 0; rb < 4; ++rb) {
-        const int xi = 4 * ra + rb;
-        if constexpr (CIN == 16)
-          U_s[xi * (16 * COUT) + (((ci >> 2) & 3) * COUT + co) * 4 + (ci & 3)] = u[rb];
-        else
-          U_s[(xi * 4 + ci) * COUT + co] = u[rb];
-      }
+      for (int xi = 0; xi < 16; ++xi) U_s[(xi * 4 + ci) * COUT + co] = u[xi];
     }
   }
 
@@ -975,14 +845,7 @@ __global__ __launch_bounds__((64 * PoolGeo<CIN, COUT, RT>::NW), 3) void wino_con
 
   // staging: the generic kernel's register prefetch (row table in LDS)
   int sl_L[MAXC], sl_x[MAXC];
-#pragma unroll
-  for (int k = 0; k < MAXC; ++k) {
-    const int e = threadIdx.x + k * NTH;
-    const int ch = e & (C4 - 1), pix = e >> LC4;
-    const int L = pix / Wl, col = pix - L * Wl;
-    sl_L[k] = L < P::ROWS ? L : -1;
-    sl_x[k] = (col >= 1 && col <= W) ? (col - 1) * CIN + 4 * ch : -1;
-  }
+  wino_slots<MAXC, NTH, CIN>(Wl, P::ROWS, W, sl_L, sl_x);
   auto build_tab = [&](int rr) {
     const int n = rr / KP, k = rr - n * KP;
     const int L = threadIdx.x;
@@ -994,12 +857,7 @@ __global__ __launch_bounds__((64 * PoolGeo<CIN, COUT, RT>::NW), 3) void wino_con
   f4 stg[MAXC];
   const auto srcr = buf_rsrc(a.src, static_cast<int64_t>(a.N) * a.H * W * CIN);
   auto prefetch = [&]() __attribute__((always_inline)) {
-#pragma unroll
-    for (int k = 0; k < MAXC; ++k) {
-      const int rb = sl_L[k] >= 0 ? tab_s[sl_L[k]] : -1;
-      const bool in = rb >= 0 && sl_x[k] >= 0;
-      stg[k] = bload(srcr, in ? static_cast<uint32_t>(rb + sl_x[k]) * 4u : kOOB);
-    }
+    wino_prefetch(srcr, tab_s, sl_L, sl_x, false, stg);
   };
   build_tab(r);
   __syncthreads();
@@ -1062,63 +920,16 @@ __global__ __launch_bounds__((64 * PoolGeo<CIN, COUT, RT>::NW), 3) void wino_con
     for (int xi = 0; xi < 16; ++xi) acc[xi] = f4{0.f, 0.f, 0.f, 0.f};
     if (!knob(a.ablate, 1)) {
       if constexpr (CIN == 16) {
-        constexpr int USTR = 16 * COUT;  // floats per xi
-        f4 d[16];
-#pragma unroll
-        for (int dy = 0; dy < 4; ++dy)
-#pragma unroll
-          for (int dx = 0; dx < 4; ++dx)
-            d[4 * dy + dx] = *reinterpret_cast<const f4*>(xp + dy * rowstr + dx * PP);
-        f4 s[16];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          s[q] = d[q] - d[8 + q];
-          s[4 + q] = d[4 + q] + d[8 + q];
-          s[8 + q] = d[8 + q] - d[4 + q];
-          s[12 + q] = d[4 + q] - d[12 + q];
-        }
-        f4 V[16];
-#pragma unroll
-        for (int ra = 0; ra < 4; ++ra) {
-          V[4 * ra + 0] = s[4 * ra + 0] - s[4 * ra + 2];
-          V[4 * ra + 1] = s[4 * ra + 1] + s[4 * ra + 2];
-          V[4 * ra + 2] = s[4 * ra + 2] - s[4 * ra + 1];
-          V[4 * ra + 3] = s[4 * ra + 1] - s[4 * ra + 3];
-        }
-#pragma unroll
-        for (int xp2 = 0; xp2 < 8; ++xp2) {
-          f4 ua[2];
-#pragma unroll
-          for (int q = 0; q < 2; ++q)
-            ua[q] = *reinterpret_cast<const f4*>(up + (2 * xp2 + q) * USTR);
-#pragma unroll
-          for (int v = 0; v < 4; ++v)
-#pragma unroll
-            for (int q = 0; q < 2; ++q)
-              acc[2 * xp2 + q] = mfma4(ua[q][v], V[2 * xp2 + q][v], acc[2 * xp2 + q]);
-        }
+        const F16 V = wino_input_transform(wino_load_patch(xp, rowstr, PP));
+        wino_mfma_block<false>(up, 16 * COUT, V.v, acc);
       } else {
-        float d[16];
+        Tile16<float> d;
 #pragma unroll
         for (int dy = 0; dy < 4; ++dy)
 #pragma unroll
-          for (int dx = 0; dx < 4; ++dx) d[4 * dy + dx] = xp[dy * Wl + dx];
-        float s[16];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          s[q] = d[q] - d[8 + q];
-          s[4 + q] = d[4 + q] + d[8 + q];
-          s[8 + q] = d[8 + q] - d[4 + q];
-          s[12 + q] = d[4 + q] - d[12 + q];
-        }
-        float V[16];
-#pragma unroll
-        for (int ra = 0; ra < 4; ++ra) {
-          V[4 * ra + 0] = s[4 * ra + 0] - s[4 * ra + 2];
-          V[4 * ra + 1] = s[4 * ra + 1] + s[4 * ra + 2];
-          V[4 * ra + 2] = s[4 * ra + 2] - s[4 * ra + 1];
-          V[4 * ra + 3] = s[4 * ra + 1] - s[4 * ra + 3];
-        }
+          for (int dx = 0; dx < 4; ++dx) d.v[4 * dy + dx] = xp[dy * Wl + dx];
+        const Tile16<float> Vs = wino_input_transform(d);
+        const float (&V)[16] = Vs.v;
         float ua[16];
 #pragma unroll
         for (int xi = 0; xi < 16; ++xi) ua[xi] = up[xi * 4 * COUT];
@@ -1132,18 +943,8 @@ __global__ __launch_bounds__((64 * PoolGeo<CIN, COUT, RT>::NW), 3) void wino_con
     {
       const int kk = cur - (cur / KP) * KP;  // this range's tile-row pair
       const bool row_ok = !OT || 2 * kk + tyl < a.TY;
-      f4 tt[4][2];
-#pragma unroll
-      for (int ra = 0; ra < 4; ++ra) {
-        tt[ra][0] = (acc[4 * ra] + acc[4 * ra + 1]) + acc[4 * ra + 2];
-        tt[ra][1] = (acc[4 * ra + 1] - acc[4 * ra + 2]) - acc[4 * ra + 3];
-      }
-      f4 Y[4];
-#pragma unroll
-      for (int c = 0; c < 2; ++c) {
-        Y[c] = (tt[0][c] + tt[1][c]) + tt[2][c];
-        Y[2 + c] = (tt[1][c] - tt[2][c]) - tt[3][c];
-      }
+      const F4x4 Ys = wino_output_transform(acc);
+      const f4 (&Y)[4] = Ys.v;
 #pragma unroll
       for (int dy = 0; dy < 2; ++dy)
 #pragma unroll
@@ -1344,31 +1145,9 @@ __global__ __launch_bounds__(512, 1) void wino_conv_pool_img_kernel(WinoPoolArgs
   float* img = x_s;
   int* tab_s = reinterpret_cast<int*>(x_s + P::XREG);
 
-  for (int e = threadIdx.x; e < CIN * COUT; e += NTH) {
-    const int co = e % COUT, ci = e / COUT;
-    float gk[3][3];
-#pragma unroll
-    for (int ky = 0; ky < 3; ++ky)
-#pragma unroll
-      for (int kx = 0; kx < 3; ++kx) gk[ky][kx] = a.w[((ky * 3 + kx) * CIN + ci) * COUT + co];
-    float t[4][3];
-#pragma unroll
-    for (int kx = 0; kx < 3; ++kx) {
-      t[0][kx] = gk[0][kx];
-      t[1][kx] = 0.5f * ((gk[0][kx] + gk[1][kx]) + gk[2][kx]);
-      t[2][kx] = 0.5f * ((gk[0][kx] - gk[1][kx]) + gk[2][kx]);
-      t[3][kx] = gk[2][kx];
-    }
-    const int b = ci >> 4, gq = (ci >> 2) & 3, v = ci & 3;
-#pragma unroll
-    for (int ra = 0; ra < 4; ++ra) {
-      const float u[4] = {t[ra][0], 0.5f * ((t[ra][0] + t[ra][1]) + t[ra][2]),
-                          0.5f * ((t[ra][0] - t[ra][1]) + t[ra][2]), t[ra][2]};
-#pragma unroll
-      for (int rb = 0; rb < 4; ++rb)
-        U_s[(4 * ra + rb) * USTR + ((b * 4 + gq) * COUT + co) * 4 + v] = u[rb];
-    }
-  }
+  wino_u_to_lds<NB, COUT, NTH>(U_s, CIN * COUT, [&](int ky, int kx, int ci, int co) {
+    return a.w[((ky * 3 + kx) * CIN + ci) * COUT + co];
+  });
 
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int g = lane >> 4, c16 = lane & 15;
@@ -1437,55 +1216,14 @@ __global__ __launch_bounds__(512, 1) void wino_conv_pool_img_kernel(WinoPoolArgs
       if (task < NTASK) {
 #pragma unroll
         for (int b = 0; b < NB; ++b) {
-          f4 d[16];
-#pragma unroll
-          for (int dy = 0; dy < 4; ++dy)
-#pragma unroll
-            for (int dx = 0; dx < 4; ++dx)
-              d[4 * dy + dx] = *reinterpret_cast<const f4*>(xp + dy * rowstr + dx * PP + 16 * b);
-          f4 s[16];
-#pragma unroll
-          for (int q = 0; q < 4; ++q) {
-            s[q] = d[q] - d[8 + q];
-            s[4 + q] = d[4 + q] + d[8 + q];
-            s[8 + q] = d[8 + q] - d[4 + q];
-            s[12 + q] = d[4 + q] - d[12 + q];
-          }
-          f4 V[16];
-#pragma unroll
-          for (int ra = 0; ra < 4; ++ra) {
-            V[4 * ra + 0] = s[4 * ra + 0] - s[4 * ra + 2];
-            V[4 * ra + 1] = s[4 * ra + 1] + s[4 * ra + 2];
-            V[4 * ra + 2] = s[4 * ra + 2] - s[4 * ra + 1];
-            V[4 * ra + 3] = s[4 * ra + 1] - s[4 * ra + 3];
-          }
-          const float* ub = up + b * 4 * COUT * 4;
-#pragma unroll
-          for (int xp2 = 0; xp2 < 8; ++xp2) {
-            f4 ua[2];
-#pragma unroll
-            for (int q = 0; q < 2; ++q)
-              ua[q] = *reinterpret_cast<const f4*>(ub + (2 * xp2 + q) * USTR);
-#pragma unroll
-            for (int v = 0; v < 4; ++v)
-#pragma unroll
-              for (int q = 0; q < 2; ++q)
-                acc[2 * xp2 + q] = mfma4(ua[q][v], V[2 * xp2 + q][v], acc[2 * xp2 + q]);
-          }
+          const F16 V = wino_input_transform(wino_load_patch(xp + 16 * b, rowstr, PP));
+          wino_mfma_block<false>(up + b * 4 * COUT * 4, USTR, V.v, acc);
         }
       }
-      f4 tt[4][2];
-#pragma unroll
-      for (int ra = 0; ra < 4; ++ra) {
-        tt[ra][0] = (acc[4 * ra] + acc[4 * ra + 1]) + acc[4 * ra + 2];
-        tt[ra][1] = (acc[4 * ra + 1] - acc[4 * ra + 2]) - acc[4 * ra + 3];
-      }
       const f4 bv = *reinterpret_cast<const f4*>(a.bias + (co0 < COUT ? co0 : 0) + 4 * g);
+      const F4x4 Ys = wino_output_transform(acc);
 #pragma unroll
-      for (int c = 0; c < 2; ++c) {
-        Yt[i][c] = (tt[0][c] + tt[1][c]) + tt[2][c] + bv;
-        Yt[i][2 + c] = (tt[1][c] - tt[2][c]) - tt[3][c] + bv;
-      }
+      for (int q = 0; q < 4; ++q) Yt[i][q] = Ys.v[q] + bv;
     }
     __syncthreads();  // every wave's patch reads are done: x_s becomes the image
 #pragma unroll
@@ -1591,6 +1329,8 @@ __host__ __device__ constexpr bool wg_need_row(int XR, int XG, int dy) {
           : XG == 3 ? (dy == 1 || dy == 3) : (dy == 1 || dy == 2));
 }
 
+// (Own text of the row transforms and the epilogue: on the shared forms the
+// 32 -> 32 instance measured 1.5-2 % slower, profiles/experiments.md.)
 template <int CIN, int COUT, int XR, int RT, int MAXCX, int MAXCD>
 __global__ __launch_bounds__(256, 1) void wino_wgrad_kernel(WinoWgArgs a) {
   constexpr int NW = 4, NTH = 256;
@@ -1977,6 +1717,11 @@ struct WinoBwdArgs {
 // RT / 4 k-steps evenly.  NW = 12 over 96-tile ranges (three waves per SIMD)
 // does not fit: capped at 168 VGPRs the kernel spills 121 (it needs ~256 at
 // two waves per SIMD), so only NW = 8 is instantiated.
+// (The weight transform and the slot table are the shared ones.  The data-
+// gradient half keeps its own text: on wino_tile, arrays by reference or by
+// value, the six default instances spill more (6 -> 9, 0 -> 4).  So does the
+// prefetch: on wino_prefetch the res16 backward measured 8 % slower.
+// profiles/experiments.md.)
 template <int C, int RT, int MAXC, int KD, bool WWG = false, bool RELU = false, int NW = 8,
           int GH = 0, int GW = 0>
 __global__ __launch_bounds__(64 * NW, WWG ? 1 : 2) void wino_bwd_fused_kernel(WinoBwdArgs a) {
@@ -2004,30 +1749,10 @@ __global__ __launch_bounds__(64 * NW, WWG ? 1 : 2) void wino_bwd_fused_kernel(Wi
   int* tile_s = tab_s + G.maxrows;                                // [RT]
 
   // U = G g' G^T of the flipped / transposed weights (the dgrad conv)
-  for (int e = threadIdx.x; e < C * C; e += NTH) {
-    const int co = e % C, ci = e / C;  // ci = dY channel, co = dX channel
-    float gk[3][3];
-#pragma unroll
-    for (int ky = 0; ky < 3; ++ky)
-#pragma unroll
-      for (int kx = 0; kx < 3; ++kx) gk[ky][kx] = a.w[(((2 - ky) * 3 + (2 - kx)) * C + co) * C + ci];
-    float t[4][3];
-#pragma unroll
-    for (int kx = 0; kx < 3; ++kx) {
-      t[0][kx] = gk[0][kx];
-      t[1][kx] = 0.5f * ((gk[0][kx] + gk[1][kx]) + gk[2][kx]);
-      t[2][kx] = 0.5f * ((gk[0][kx] - gk[1][kx]) + gk[2][kx]);
-      t[3][kx] = gk[2][kx];
-    }
-    const int gq = (ci >> 2) & 3, v = ci & 3;
-#pragma unroll
-    for (int ra = 0; ra < 4; ++ra) {
-      const float u[4] = {t[ra][0], 0.5f * ((t[ra][0] + t[ra][1]) + t[ra][2]),
-                          0.5f * ((t[ra][0] - t[ra][1]) + t[ra][2]), t[ra][2]};
-#pragma unroll
-      for (int rb = 0; rb < 4; ++rb) U_s[(4 * ra + rb) * USTR + (gq * C + co) * 4 + v] = u[rb];
-    }
-  }
+  // (ci = dY channel, co = dX channel)
+  wino_u_to_lds<1, C, NTH>(U_s, C * C, [&](int ky, int kx, int ci, int co) {
+    return a.w[(((2 - ky) * 3 + (2 - kx)) * C + co) * C + ci];
+  });
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int g = lane >> 4, c16 = lane & 15;
 
@@ -2041,14 +1766,7 @@ __global__ __launch_bounds__(64 * NW, WWG ? 1 : 2) void wino_bwd_fused_kernel(Wi
 
   // staging slots: element e of both images = (row L, col, quad)
   int sl_L[MAXC], sl_o[MAXC];
-#pragma unroll
-  for (int k = 0; k < MAXC; ++k) {
-    const int e = threadIdx.x + k * NTH;
-    const int ch = e & (C4 - 1), pix = e >> LC4;
-    const int L = pix / G.WL0, col = pix - L * G.WL0;
-    sl_L[k] = L < G.maxrows ? L : -1;
-    sl_o[k] = (col >= 1 && col <= G.W) ? (col - 1) * C + 4 * ch : -1;
-  }
+  wino_slots<MAXC, NTH, C>(G.WL0, G.maxrows, G.W, sl_L, sl_o);
   auto build_tab = [&](int rr) {
     const RangeGeom gm = G.range(rr);
     const int L = threadIdx.x;
@@ -2397,6 +2115,9 @@ constexpr bool fused32_pad() {
   }
 }
 
+// (The weight transform and the slot tables are the shared ones.  The rest
+// keeps its own text: on the shared functions one instance, <16, 16, 64, 5, 5,
+// false, false, 36, 64>, went from 168 to 180 VGPRs, 3 -> 2 waves.)
 template <int CX, int CY, int RT, int MAXCX, int MAXCY, bool RELU, bool MASK, int GH = 0,
           int GW = 0>
 __global__ __launch_bounds__(512, 2) void wino_bwd_fused32_kernel(WinoBwdArgs a) {
@@ -2429,31 +2150,10 @@ __global__ __launch_bounds__(512, 2) void wino_bwd_fused32_kernel(WinoBwdArgs a)
 
   // U = G g' G^T of the flipped / transposed weights (the dgrad conv);
   // forward weights HWIO [3][3][CX][CY]
-  for (int e = threadIdx.x; e < CX * CY; e += NTH) {
-    const int co = e % CX, ci = e / CX;  // ci = dY channel, co = dX channel
-    float gk[3][3];
-#pragma unroll
-    for (int ky = 0; ky < 3; ++ky)
-#pragma unroll
-      for (int kx = 0; kx < 3; ++kx) gk[ky][kx] = a.w[(((2 - ky) * 3 + (2 - kx)) * CX + co) * CY + ci];
-    float t[4][3];
-#pragma unroll
-    for (int kx = 0; kx < 3; ++kx) {
-      t[0][kx] = gk[0][kx];
-      t[1][kx] = 0.5f * ((gk[0][kx] + gk[1][kx]) + gk[2][kx]);
-      t[2][kx] = 0.5f * ((gk[0][kx] - gk[1][kx]) + gk[2][kx]);
-      t[3][kx] = gk[2][kx];
-    }
-    const int b = ci >> 4, gq = (ci >> 2) & 3, v = ci & 3;
-#pragma unroll
-    for (int ra = 0; ra < 4; ++ra) {
-      const float u[4] = {t[ra][0], 0.5f * ((t[ra][0] + t[ra][1]) + t[ra][2]),
-                          0.5f * ((t[ra][0] - t[ra][1]) + t[ra][2]), t[ra][2]};
-#pragma unroll
-      for (int rb = 0; rb < 4; ++rb)
-        U_s[(4 * ra + rb) * USTR + ((b * 4 + gq) * CX + co) * 4 + v] = u[rb];
-    }
-  }
+  // (ci = dY channel, co = dX channel)
+  wino_u_to_lds<NBY, CX, NTH>(U_s, CX * CY, [&](int ky, int kx, int ci, int co) {
+    return a.w[(((2 - ky) * 3 + (2 - kx)) * CX + co) * CY + ci];
+  });
   if (threadIdx.x < 2) flag_s[threadIdx.x] = 0;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int g = lane >> 4, c16 = lane & 15;
@@ -2469,22 +2169,8 @@ __global__ __launch_bounds__(512, 2) void wino_bwd_fused32_kernel(WinoBwdArgs a)
 
   // staging slots: element e = (row L, col, quad) of the dY image and of x
   int sy_L[MAXCY], sy_o[MAXCY], sx_L[MAXCX], sx_o[MAXCX];
-#pragma unroll
-  for (int k = 0; k < MAXCY; ++k) {
-    const int e = threadIdx.x + k * NTH;
-    const int ch = e & (C4Y - 1), pix = e >> LC4Y;
-    const int L = pix / G.WL0, col = pix - L * G.WL0;
-    sy_L[k] = L < G.maxrows ? L : -1;
-    sy_o[k] = (col >= 1 && col <= G.W) ? (col - 1) * CY + 4 * ch : -1;
-  }
-#pragma unroll
-  for (int k = 0; k < MAXCX; ++k) {
-    const int e = threadIdx.x + k * NTH;
-    const int ch = e & (C4X - 1), pix = e >> LC4X;
-    const int L = pix / G.WL0, col = pix - L * G.WL0;
-    sx_L[k] = L < G.maxrows ? L : -1;
-    sx_o[k] = (col >= 1 && col <= G.W) ? (col - 1) * CX + 4 * ch : -1;
-  }
+  wino_slots<MAXCY, NTH, CY>(G.WL0, G.maxrows, G.W, sy_L, sy_o);
+  wino_slots<MAXCX, NTH, CX>(G.WL0, G.maxrows, G.W, sx_L, sx_o);
   // row table: global PIXEL index (n H + y) W of LDS row L, or -1
   auto build_tab = [&](int rr) __attribute__((always_inline)) {
     const RangeGeom gm = G.range(rr);
@@ -3005,10 +2691,11 @@ bool run_wino_bwd(const float* dy, const float* w, const float* x, const float* 
 // and computes y from the t image.  Workgroups are independent; the only
 // synchronisation is __syncthreads.
 //
-// Per output element the arithmetic is wino_conv_kernel's (the expressions
-// below are copies of its weight / input / output transforms, its MFMA
-// k-step order and its epilogue order: bias, residual, ReLU), so the result
-// is bitwise that of the two launches (tests/test_res_block_f32_gpu.py).
+// Per output element the arithmetic is wino_conv_kernel's: both call the
+// same weight / input / output transforms (wino_core.h), wino_mfma_block is
+// that kernel's k-step order, and the epilogue order is the same (bias,
+// residual, ReLU), so the result is bitwise that of the two launches
+// (tests/test_res_block_f32_gpu.py).
 struct ResBlockArgs {
   const float* x;   // [N, H, W, C]
   const float* w1;  // HWIO [3, 3, C, C]
@@ -3020,102 +2707,11 @@ struct ResBlockArgs {
   float rTX, rWl;
 };
 
-// U = G g G^T of w into U_s as MFMA A fragments [16 xi][C/16][4 g][C][4]
-template <int C, int NTH>
-__device__ __forceinline__ void res_u_transform(const float* __restrict__ w, float* U_s) {
-  constexpr int USTR = C * C;
-  for (int e = threadIdx.x; e < C * C; e += NTH) {
-    const int co = e % C, ci = e / C;
-    float gk[3][3];
-#pragma unroll
-    for (int ky = 0; ky < 3; ++ky)
-#pragma unroll
-      for (int kx = 0; kx < 3; ++kx) gk[ky][kx] = w[((ky * 3 + kx) * C + ci) * C + co];
-    float t[4][3];
-#pragma unroll
-    for (int kx = 0; kx < 3; ++kx) {
-      t[0][kx] = gk[0][kx];
-      t[1][kx] = 0.5f * ((gk[0][kx] + gk[1][kx]) + gk[2][kx]);
-      t[2][kx] = 0.5f * ((gk[0][kx] - gk[1][kx]) + gk[2][kx]);
-      t[3][kx] = gk[2][kx];
-    }
-    const int b = ci >> 4, gq = (ci >> 2) & 3, v = ci & 3;
-#pragma unroll
-    for (int ra = 0; ra < 4; ++ra) {
-      const float u[4] = {t[ra][0], 0.5f * ((t[ra][0] + t[ra][1]) + t[ra][2]),
-                          0.5f * ((t[ra][0] - t[ra][1]) + t[ra][2]), t[ra][2]};
-#pragma unroll
-      for (int rb = 0; rb < 4; ++rb)
-        U_s[(4 * ra + rb) * USTR + ((b * 4 + gq) * C + co) * 4 + v] = u[rb];
-    }
-  }
-}
-
-// One (16 tiles x 16 output channels) task: Y[2 dy + dx] = A^T M A with
-// M[xi] = sum_ci U[xi][co][ci] (B^T d B)[xi][ci].  xp: the lane's 4x4 patch
-// (tile = lane & 15, channel quad = lane >> 4) in an LDS image of pixel pitch
-// C + 4; up: the lane's A fragments.  RELU: ReLU on the patch values.
+// One (16 tiles x 16 output channels) task of either conv (wino_tile over an
+// LDS image of pixel pitch C + 4, U as [16 xi][C/16][4 g][C][4])
 template <int C, bool RELU>
-__device__ __forceinline__ void res_tile(const float* xp, int rowstr, const float* up, f4 (&Y)[4]) {
-  constexpr int PP = C + 4, NB = C / 16, USTR = C * C;
-  f4 acc[16];
-#pragma unroll
-  for (int xi = 0; xi < 16; ++xi) acc[xi] = f4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-  for (int b = 0; b < NB; ++b) {
-    f4 d[16];
-#pragma unroll
-    for (int dy = 0; dy < 4; ++dy)
-#pragma unroll
-      for (int dx = 0; dx < 4; ++dx) {
-        f4 v = *reinterpret_cast<const f4*>(xp + dy * rowstr + dx * PP + 16 * b);
-        if constexpr (RELU) {
-#pragma unroll
-          for (int q = 0; q < 4; ++q) v[q] = relu0(v[q]);
-        }
-        d[4 * dy + dx] = v;
-      }
-    f4 s[16];
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      s[q] = tsub(d[q], d[8 + q]);
-      s[4 + q] = tadd(d[4 + q], d[8 + q]);
-      s[8 + q] = tsub(d[8 + q], d[4 + q]);
-      s[12 + q] = tsub(d[4 + q], d[12 + q]);
-    }
-    f4 V[16];
-#pragma unroll
-    for (int ra = 0; ra < 4; ++ra) {
-      V[4 * ra + 0] = tsub(s[4 * ra + 0], s[4 * ra + 2]);
-      V[4 * ra + 1] = tadd(s[4 * ra + 1], s[4 * ra + 2]);
-      V[4 * ra + 2] = tsub(s[4 * ra + 2], s[4 * ra + 1]);
-      V[4 * ra + 3] = tsub(s[4 * ra + 1], s[4 * ra + 3]);
-    }
-    const float* ub = up + b * 4 * C * 4;
-#pragma unroll
-    for (int xp2 = 0; xp2 < 8; ++xp2) {
-      f4 ua[2];
-#pragma unroll
-      for (int q = 0; q < 2; ++q)
-        ua[q] = *reinterpret_cast<const f4*>(ub + (2 * xp2 + q) * USTR);
-#pragma unroll
-      for (int v = 0; v < 4; ++v)
-#pragma unroll
-        for (int q = 0; q < 2; ++q)
-          acc[2 * xp2 + q] = mfma4x<1>(ua[q][v], V[2 * xp2 + q][v], acc[2 * xp2 + q], v);
-    }
-  }
-  f4 tt[4][2];
-#pragma unroll
-  for (int ra = 0; ra < 4; ++ra) {
-    tt[ra][0] = tadd(tadd(acc[4 * ra], acc[4 * ra + 1]), acc[4 * ra + 2]);
-    tt[ra][1] = tsub(tsub(acc[4 * ra + 1], acc[4 * ra + 2]), acc[4 * ra + 3]);
-  }
-#pragma unroll
-  for (int c = 0; c < 2; ++c) {
-    Y[c] = tadd(tadd(tt[0][c], tt[1][c]), tt[2][c]);
-    Y[2 + c] = tsub(tsub(tt[1][c], tt[2][c]), tt[3][c]);
-  }
+__device__ __forceinline__ F4x4 res_tile(const float* xp, int rowstr, const float* up) {
+  return wino_tile<C / 16, RELU, true>(xp, rowstr, C + 4, up, C * C, 4 * C * 4);
 }
 
 // LDS of one workgroup: U, the x rows and the t rows
@@ -3164,7 +2760,12 @@ __global__ __launch_bounds__(64 * NW) void wino_res_block_kernel(ResBlockArgs a)
   }
   for (int e = threadIdx.x; e < TR * rowstr / 4; e += NTH)
     reinterpret_cast<f4*>(t_s)[e] = f4{0.f, 0.f, 0.f, 0.f};
-  res_u_transform<C, NTH>(a.w1, U_s);
+  auto u_transform = [&](const float* __restrict__ w) __attribute__((always_inline)) {
+    wino_u_to_lds<C / 16, C, NTH>(U_s, C * C, [&](int ky, int kx, int ci, int co) {
+      return w[((ky * 3 + kx) * C + ci) * C + co];
+    });
+  };
+  u_transform(a.w1);
   __syncthreads();
 
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -3185,9 +2786,9 @@ __global__ __launch_bounds__(64 * NW) void wino_res_block_kernel(ResBlockArgs a)
       if (!valid) t = 0;
       const int tr = fdivi(t, a.rTX), tx = t - tr * a.TX;
       const int tyl = lo + tr;
-      f4 Y[4];
-      res_tile<C, true>(x_s + (2 * tyl * Wl + 2 * tx) * PP + 4 * g, rowstr,
-                        U_s + (g * C + co0 + c16) * 4, Y);
+      const F4x4 Ys = res_tile<C, true>(x_s + (2 * tyl * Wl + 2 * tx) * PP + 4 * g, rowstr,
+                                        U_s + (g * C + co0 + c16) * 4);
+      const f4 (&Y)[4] = Ys.v;
       const int co = co0 + 4 * g;
       const f4 bv = *reinterpret_cast<const f4*>(a.b1 + co);
 #pragma unroll
@@ -3204,7 +2805,7 @@ __global__ __launch_bounds__(64 * NW) void wino_res_block_kernel(ResBlockArgs a)
     }
   }
   __syncthreads();  // t complete, every wave done with w1's U
-  res_u_transform<C, NTH>(a.w2, U_s);
+  u_transform(a.w2);
   __syncthreads();
 
   // ---- conv2 over the band's tile rows: local tile row tyl is tile row
@@ -3218,9 +2819,9 @@ __global__ __launch_bounds__(64 * NW) void wino_res_block_kernel(ResBlockArgs a)
       const bool valid = t < nt;
       if (!valid) t = 0;
       const int tyl = fdivi(t, a.rTX), tx = t - tyl * a.TX;
-      f4 Y[4];
-      res_tile<C, false>(t_s + ((2 * tyl + 1) * Wl + 2 * tx) * PP + 4 * g, rowstr,
-                         U_s + (g * C + co0 + c16) * 4, Y);
+      const F4x4 Ys = res_tile<C, false>(t_s + ((2 * tyl + 1) * Wl + 2 * tx) * PP + 4 * g,
+                                         rowstr, U_s + (g * C + co0 + c16) * 4);
+      const f4 (&Y)[4] = Ys.v;
       const int co = co0 + 4 * g;
       const f4 bv = *reinterpret_cast<const f4*>(a.b2 + co);
 #pragma unroll
