@@ -520,6 +520,12 @@ void register_conv_f32_ops(pybind11::module& m) {
   // 1: compile-time-geometry Winograd instances where the map has one
   // (default), 0: runtime geometry everywhere; returns the previous setting
   m.def("cf32_wino_geo", [](int v) { return sa::cf32::conv_wino_geo(v); });
+  // 1: the fused32 backward keeps the rows a range shares with the previous
+  // one in LDS (default), 0: every range stages all its rows; returns the
+  // previous setting
+  m.def("cf32_wino_keep", [](int v) { return sa::cf32::conv_wino_keep(v); });
+  // fused32 backward launches so far that ran the row-keeping instance
+  m.def("cf32_wino_keep_launches", []() { return sa::cf32::conv_wino_keep_launches(); });
   // R CUs per XCD left out of every persistent conv grid (-1 reads)
   m.def("cf32_cu_reserve", [](int r) { return sa::cf32::conv_cu_reserve(r); });
   // deferred weight-gradient reductions: defer(True) ... flush() -> one launch

@@ -105,6 +105,12 @@ int conv_wino_fault(int v);
 // Compile-time-geometry Winograd instances on (1) / off (0); returns the old
 // setting (tests compare both forms bitwise).
 int conv_wino_geo(int v);
+// Row-keeping stager of the fused32 backward on (1) / off (0); returns the
+// old setting (tests compare both bitwise).
+int conv_wino_keep(int v);
+// Fused32 backward launches so far that ran the row-keeping instance (the
+// launcher runs the plain stager where a shape does not fit; tests).
+int64_t conv_wino_keep_launches();
 // CUs the persistent conv grids are sized for: 256 - 8 R, where R CUs per
 // XCD are left to a concurrently running stream (the time-chunked LSTM
 // pipeline).  conv_cu_reserve(R) sets R (0..16; -1 reads) and returns the

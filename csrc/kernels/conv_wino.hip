@@ -45,6 +45,7 @@
 
 #include <algorithm>
 #include <cstdlib>
+#include <numeric>
 
 namespace sa {
 namespace cf32 {
@@ -571,6 +572,14 @@ int g_wino_geo = -1;  // -1: not read yet; conv_wino_geo() sets it (tests)
 bool wino_geo_enabled() {
   if (g_wino_geo < 0) g_wino_geo = env_knob("SA_WINO_GEO", 1) != 0 ? 1 : 0;
   return g_wino_geo != 0;
+}
+// Row-keeping stager of the fused32 backward (wino_bwd_fused32_kernel KEEP):
+// SA_WINO_KEEP=0 restores the stager that re-stages every row of every range.
+int g_wino_keep = -1;  // -1: not read yet; conv_wino_keep() sets it (tests)
+int64_t g_wino_keep_launches = 0;  // launches of a KEEP instance (tests)
+bool wino_keep_enabled() {
+  if (g_wino_keep < 0) g_wino_keep = env_knob("SA_WINO_KEEP", 1) != 0 ? 1 : 0;
+  return g_wino_keep != 0;
 }
 // per kernel family (SA_WINO_GEO_MASK, sweeps): bit 0 the forward, bit 1 the
 // 16-channel fused backward, bit 2 the fused32 backward
@@ -2115,11 +2124,58 @@ constexpr bool fused32_pad() {
   }
 }
 
+// Row-keeping stager: staging slots (f4 per lane) of x / dY, sized to the
+// new rows of a range that continues a run (32 -> 32: 6 rows at 18x24; the
+// 16 -> 32 head: 4 dY rows of 400 quads at 36x48; 16 -> 16 over 64 tiles: 6)
+constexpr int fused32_keep_slots(int CX, int CY, bool dy) {
+  return CX == 16 && CY == 32 ? (dy ? 4 : 2) : 3;
+}
+// its extra LDS: the four-row tile table and the two slot tables
+constexpr size_t fused32_keep_lds(int RT, int maxrows) {
+  return sizeof(int) * (4 + 3 * RT + 2 * maxrows);
+}
+// Host check of a shape: every range's image rows [A, B] (the kernel's span())
+// fit the maxrows - 1 row slots, and a range that shares rows with its
+// predecessor brings at most krows new ones (one chunk).  The row pattern
+// repeats every lcm(tiles per image, RT) tiles.
+inline bool fused32_keep_fits(int RT, int H, int TX, int TY, int64_t NT, int nranges, int maxrows,
+                              int krows) {
+  const int nslots = maxrows - 1;
+  if (krows < 1 || nslots < 2) return false;
+  const int64_t per_img = static_cast<int64_t>(TX) * TY;
+  const int64_t period = per_img / std::gcd(per_img, static_cast<int64_t>(RT));
+  const int64_t nchk = std::min<int64_t>(nranges, period + 1);
+  int64_t prevB = -1;
+  for (int64_t r = 0; r < nchk; ++r) {
+    const int64_t t0 = r * RT, t1 = std::min<int64_t>(t0 + RT, NT);
+    const int64_t R0 = t0 / TX, R1 = (t1 - 1) / TX;
+    const int64_t n0 = R0 / TY, n1 = R1 / TY;
+    const int64_t A = n0 * H + std::max<int64_t>(2 * (R0 - n0 * TY) - 1, 0);
+    const int64_t B = n1 * H + std::min<int64_t>(2 * (R1 - n1 * TY) + 2, H - 1);
+    if (B - A + 1 > nslots) return false;
+    if (r > 0 && A <= prevB && B - prevB > krows) return false;
+    prevB = B;
+  }
+  return true;
+}
+
 // (The weight transform and the slot tables are the shared ones.  The rest
 // keeps its own text: on the shared functions one instance, <16, 16, 64, 5, 5,
 // false, false, 36, 64>, went from 168 to 180 VGPRs, 3 -> 2 waves.)
+//
+// KEEP (SA_WINO_KEEP, the default): the staged rows live in a pool of
+// maxrows - 1 LDS row slots plus one all-zero row.  Image row gy = n H + y
+// always sits in slot gy % (maxrows - 1), so the rows a range shares with the
+// previous range of the run (its halo and the tile row it started in) are
+// already in place and only the NEW image rows are loaded and committed, in
+// chunks of what MAXCX / MAXCY slots hold (one chunk per range where the
+// launcher's check passes; the first range of a run and a range that shares
+// nothing take more, the extra ones exposed).  Rows outside the image all
+// map to the zero row, and the tile table holds the pixel base of each of a
+// patch's four rows.  LDS values, MFMA order and the reductions are those of
+// the plain stager: bitwise the same results (tests/test_wino_keep_gpu.py).
 template <int CX, int CY, int RT, int MAXCX, int MAXCY, bool RELU, bool MASK, int GH = 0,
-          int GW = 0>
+          int GW = 0, bool KEEP = false>
 __global__ __launch_bounds__(512, 2) void wino_bwd_fused32_kernel(WinoBwdArgs a) {
   constexpr int NW = 8, NTH = 512;
   const TileGeo<GH, GW, RT, fused32_pad<CX, CY, RT, GH, GW>()> G(a.H, a.W, a.TY, a.TX, a.NT,
@@ -2147,6 +2203,13 @@ __global__ __launch_bounds__(512, 2) void wino_bwd_fused32_kernel(WinoBwdArgs a)
   int* flag_s = reinterpret_cast<int*>(ybuf + (DSPLIT == 2 ? 2 * 4 * 64 : 0));  // [2]
   int* tab_s = flag_s + 2;                   // [maxrows]
   int* tile_s = tab_s + G.maxrows;           // [RT] patch-origin pixel (row * Wl + col)
+  // KEEP: the tile table is [RT][4] (pixel base of each patch row; 16-B
+  // aligned: flag_s is), then the two slot tables [2][maxrows] (LDS pixel
+  // base of a chunk's rows, double-buffered: a commit reads its chunk's
+  // table while the next chunk's is being built)
+  i4* tile4_s = reinterpret_cast<i4*>(flag_s + ((2 + G.maxrows + 3) & ~3));
+  int* slot_s = reinterpret_cast<int*>(tile4_s + RT);
+  const int nslots = G.maxrows - 1;          // row slots; slot nslots stays zero
 
   // U = G g' G^T of the flipped / transposed weights (the dgrad conv);
   // forward weights HWIO [3][3][CX][CY]
@@ -2155,6 +2218,10 @@ __global__ __launch_bounds__(512, 2) void wino_bwd_fused32_kernel(WinoBwdArgs a)
     return a.w[(((2 - ky) * 3 + (2 - kx)) * CX + co) * CY + ci];
   });
   if (threadIdx.x < 2) flag_s[threadIdx.x] = 0;
+  if constexpr (KEEP) {
+    for (int e = threadIdx.x; e < rsy; e += NTH) d_s[nslots * rsy + e] = 0.f;
+    for (int e = threadIdx.x; e < rsx; e += NTH) x_s[nslots * rsx + e] = 0.f;
+  }
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int g = lane >> 4, c16 = lane & 15;
 
@@ -2168,9 +2235,51 @@ __global__ __launch_bounds__(512, 2) void wino_bwd_fused32_kernel(WinoBwdArgs a)
   }
 
   // staging slots: element e = (row L, col, quad) of the dY image and of x
+  // (KEEP: of the chunk's row j, at most krows rows per chunk)
+  const int krows = KEEP ? min(min(MAXCY * NTH / (G.WL0 * C4Y), MAXCX * NTH / (G.WL0 * C4X)),
+                               nslots)
+                         : G.maxrows;
   int sy_L[MAXCY], sy_o[MAXCY], sx_L[MAXCX], sx_o[MAXCX];
-  wino_slots<MAXCY, NTH, CY>(G.WL0, G.maxrows, G.W, sy_L, sy_o);
-  wino_slots<MAXCX, NTH, CX>(G.WL0, G.maxrows, G.W, sx_L, sx_o);
+  wino_slots<MAXCY, NTH, CY>(G.WL0, krows, G.W, sy_L, sy_o);
+  wino_slots<MAXCX, NTH, CX>(G.WL0, krows, G.W, sx_L, sx_o);
+  // KEEP: the slot's float offset within its LDS row
+  int sy_c[KEEP ? MAXCY : 1], sx_c[KEEP ? MAXCX : 1];
+  if constexpr (KEEP) {
+#pragma unroll
+    for (int k = 0; k < MAXCY; ++k) {
+      const int e = threadIdx.x + k * NTH, pix = e >> LC4Y;
+      sy_c[k] = (pix - (pix / G.WL0) * G.WL0) * PPY + 4 * (e & (C4Y - 1));
+    }
+#pragma unroll
+    for (int k = 0; k < MAXCX; ++k) {
+      const int e = threadIdx.x + k * NTH, pix = e >> LC4X;
+      sx_c[k] = (pix - (pix / G.WL0) * G.WL0) * PPX + 4 * (e & (C4X - 1));
+    }
+  }
+  // the image rows gy = n H + y a range's tiles read: [A, B] (contiguous:
+  // an image's last row is followed by the next image's first)
+  auto span = [&](int rr, int& A, int& B) __attribute__((always_inline)) {
+    const int t0 = rr * RT, t1 = min(t0 + RT, G.NT);
+    const int R0 = G.div_tx(t0), R1 = G.div_tx(t1 - 1);
+    const int n0 = G.div_ty(R0), n1 = G.div_ty(R1);
+    A = n0 * G.H + max(2 * (R0 - n0 * G.TY) - 1, 0);
+    B = n1 * G.H + min(2 * (R1 - n1 * G.TY) + 2, G.H - 1);
+  };
+  // KEEP row tables of the chunk of image rows S + j <= B (j < krows): the
+  // global pixel index gy W (or -1) and the row's LDS pixel base
+  int par = 1;  // slot table of the chunk in the staging registers
+  auto build_ktab = [&](int S, int B) __attribute__((always_inline)) {
+    par ^= 1;
+    const int j = threadIdx.x;
+    if (j < krows) {
+      const int gy = S + j;
+      const bool ok = gy <= B;
+      tab_s[j] = ok ? gy * G.W : -1;
+      slot_s[par * G.maxrows + j] =
+          ok ? static_cast<int>(static_cast<unsigned>(gy) % static_cast<unsigned>(nslots)) * Wl
+             : -1;
+    }
+  };
   // row table: global PIXEL index (n H + y) W of LDS row L, or -1
   auto build_tab = [&](int rr) __attribute__((always_inline)) {
     const RangeGeom gm = G.range(rr);
@@ -2203,16 +2312,96 @@ __global__ __launch_bounds__(512, 2) void wino_bwd_fused32_kernel(WinoBwdArgs a)
       sx[k] = bload(xr, in ? static_cast<uint32_t>(rb * CX + sx_o[k]) * 4u : kOOB);
     }
   };
-  build_tab(r);
+  int prevB = -1;  // KEEP: last image row the run's previous range staged
+  if constexpr (KEEP) {
+    int A, B;
+    span(r, A, B);
+    build_ktab(A, B);
+  } else {
+    build_tab(r);
+  }
   __syncthreads();
   prefetch();
+
+  // KEEP: commit the chunk in the staging registers to its rows' slots
+  auto commit_keep = [&]() __attribute__((always_inline)) {
+    const int* sl = slot_s + par * G.maxrows;
+#pragma unroll
+    for (int k = 0; k < MAXCY; ++k) {
+      const int sp = sl[sy_L[k] >= 0 ? sy_L[k] : 0];
+      if (sy_L[k] >= 0 && sp >= 0)
+        *reinterpret_cast<f4*>(d_s + sp * PPY + sy_c[k]) = sy[k];
+    }
+#pragma unroll
+    for (int k = 0; k < MAXCX; ++k) {
+      const int sp = sl[sx_L[k] >= 0 ? sx_L[k] : 0];
+      if (sx_L[k] >= 0 && sp >= 0)
+        *reinterpret_cast<f4*>(x_s + sp * PPX + sx_c[k]) = sx[k];
+    }
+  };
+  // KEEP advance: commit the range's first chunk of new rows (prefetched
+  // under the previous range), stage any further chunks (exposed), build the
+  // four-row tile table and the next range's first chunk, start its prefetch
+  auto advance_keep = [&]() __attribute__((always_inline)) {
+    __syncthreads();  // U_s written / the previous range's LDS reads are done
+    commit_keep();
+    const int cur = r;
+    ++r;
+    int A, B;
+    span(cur, A, B);
+    // (tab_s is single-buffered: its last readers, the previous prefetch,
+    // passed the barrier above; each extra chunk's prefetch is fenced from
+    // the next table build by the barrier that ends the iteration.  The slot
+    // table a build writes is the one no commit since two barriers reads.)
+    for (int S = max(A, prevB + 1) + krows; S <= B; S += krows) {
+      build_ktab(S, B);
+      __syncthreads();
+      prefetch();
+      commit_keep();
+      __syncthreads();  // this chunk's table reads are done
+    }
+    RangeGeom gm{};
+    gm.t0 = cur * RT;
+    gm.t1 = min(gm.t0 + RT, G.NT);
+    if (threadIdx.x < RT) {
+      const int t = gm.t0 + threadIdx.x;
+      i4 v = {-1, -1, -1, -1};
+      if (t < gm.t1) {
+        const int R = G.div_tx(t), tx = t - R * G.TX;
+        const int n = G.div_ty(R), ty = R - n * G.TY;
+        // patch rows y = 2 ty - 1 .. 2 ty + 2; row 1 is always in the image
+        const int y1 = 2 * ty;
+        const int s1 = static_cast<int>(static_cast<unsigned>(n * G.H + y1) %
+                                        static_cast<unsigned>(nslots));
+        const int s0 = s1 == 0 ? nslots - 1 : s1 - 1;
+        const int s2 = s1 + 1 >= nslots ? s1 + 1 - nslots : s1 + 1;
+        const int s3 = s1 + 2 >= nslots ? s1 + 2 - nslots : s1 + 2;
+        v[0] = (y1 >= 1 ? s0 : nslots) * Wl + 2 * tx;
+        v[1] = s1 * Wl + 2 * tx;
+        v[2] = (y1 + 1 < G.H ? s2 : nslots) * Wl + 2 * tx;
+        v[3] = (y1 + 2 < G.H ? s3 : nslots) * Wl + 2 * tx;
+      }
+      tile4_s[threadIdx.x] = v;
+    }
+    prevB = B;
+    if (r < r_end) {
+      int A2, B2;
+      span(r, A2, B2);
+      build_ktab(max(A2, B + 1), B2);
+    } else {
+      build_ktab(1, 0);  // nothing: every load of the last prefetch reads zeros
+    }
+    __syncthreads();
+    prefetch();  // in flight under the MFMAs below
+    return gm;
+  };
 
   // Commit the prefetched range to LDS, build its tile table and the next
   // range's row table, start the next prefetch.  Both wave roles run it
   // once per range (same barrier count); the roles are separate loops so
   // the weight-gradient accumulators are not live in the data-gradient
   // code (one loop with both would need > 256 VGPRs).
-  auto advance = [&]() __attribute__((always_inline)) {
+  auto advance_plain = [&]() __attribute__((always_inline)) {
     __syncthreads();  // U_s written / the previous range's LDS reads are done
 #pragma unroll
     for (int k = 0; k < MAXCY; ++k) {
@@ -2250,6 +2439,20 @@ __global__ __launch_bounds__(512, 2) void wino_bwd_fused32_kernel(WinoBwdArgs a)
     prefetch();  // in flight under the MFMAs below
     return gm;
   };
+  auto advance = [&]() __attribute__((always_inline)) {
+    if constexpr (KEEP) return advance_keep();
+    else return advance_plain();
+  };
+  // a tile's table entry (KEEP: the pixel base of each patch row; else the
+  // patch origin) and the float offset of its patch row i at pixel pitch pp
+  auto tile_ref = [&](int i) __attribute__((always_inline)) {
+    if constexpr (KEEP) return tile4_s[i];
+    else return tile_s[i];
+  };
+  auto row_off = [&](auto tr, int i, int pp) __attribute__((always_inline)) {
+    if constexpr (KEEP) return tr[i] * pp;
+    else return tr * pp + i * Wl * pp;
+  };
 
   const int wv = __builtin_amdgcn_readfirstlane(wave);  // wave-uniform role
   if (wv < 4) {
@@ -2268,7 +2471,7 @@ __global__ __launch_bounds__(512, 2) void wino_bwd_fused32_kernel(WinoBwdArgs a)
         if (!valid) t = gm.t0;
         const int R = G.div_tx(t), tx = t - R * G.TX;
         const int n = G.div_ty(R), ty = R - n * G.TY;
-        const int bpx = tile_s[valid ? 16 * grp + c16 : 0];
+        const auto bpx = tile_ref(valid ? 16 * grp + c16 : 0);
         const int co = 16 * cb + 4 * g;  // this lane's 4 dX channels
         f4 addv[4];
         if (half == 0) {
@@ -2286,13 +2489,14 @@ __global__ __launch_bounds__(512, 2) void wino_bwd_fused32_kernel(WinoBwdArgs a)
 #pragma unroll
         for (int bb = 0; bb < NBT; ++bb) {
           const int b = yb0 + bb;
-          const float* dp = d_s + bpx * PPY + 16 * b + 4 * g;
+          const float* dp = d_s + 16 * b + 4 * g;
           f4 d[16];
 #pragma unroll
           for (int dy = 0; dy < 4; ++dy)
 #pragma unroll
             for (int dx = 0; dx < 4; ++dx)
-              d[4 * dy + dx] = *reinterpret_cast<const f4*>(dp + dy * rsy + dx * PPY);
+              d[4 * dy + dx] =
+                  *reinterpret_cast<const f4*>(dp + row_off(bpx, dy, PPY) + dx * PPY);
           f4 sv[16];
 #pragma unroll
           for (int q = 0; q < 4; ++q) {
@@ -2368,7 +2572,7 @@ __global__ __launch_bounds__(512, 2) void wino_bwd_fused32_kernel(WinoBwdArgs a)
           }
         }
         if (half == 0) {
-          const float* xm = x_s + bpx * PPX + co;
+          const float* xm = x_s + co;
 #pragma unroll
           for (int dy = 0; dy < 2; ++dy)
 #pragma unroll
@@ -2378,7 +2582,8 @@ __global__ __launch_bounds__(512, 2) void wino_bwd_fused32_kernel(WinoBwdArgs a)
               const int64_t o = ((static_cast<int64_t>(n) * G.H + oy) * G.W + ox) * CX + co;
               f4 v = Y[2 * dy + dx];
               if constexpr (MASK) {
-                const f4 m = *reinterpret_cast<const f4*>(xm + (dy + 1) * rsx + (dx + 1) * PPX);
+                const f4 m = *reinterpret_cast<const f4*>(xm + row_off(bpx, dy + 1, PPX) +
+                                                          (dx + 1) * PPX);
 #pragma unroll
                 for (int k = 0; k < 4; ++k) v[k] = m[k] > 0.f ? v[k] : 0.f;
               }
@@ -2411,14 +2616,23 @@ __global__ __launch_bounds__(512, 2) void wino_bwd_fused32_kernel(WinoBwdArgs a)
       constexpr int AR = decltype(ARc)::value;
       constexpr bool FULL = decltype(FULLc)::value;
         for (int st = 0; st < (knob(a.ablate, 4) ? 0 : RT / 4); ++st) {
-          int bpx = tile_s[4 * st + kperm(g)];
-          const bool valid = FULL || bpx >= 0;
-          bpx = valid ? bpx : 0;
+          auto bpx = tile_ref(4 * st + kperm(g));
+          bool valid;
+          if constexpr (KEEP) {
+            // a tile past the batch's end reads the zero row (no slot is
+            // written in every range, so any other row may hold stale LDS)
+            valid = FULL || bpx[1] >= 0;
+            if (!valid) bpx = i4{nslots * Wl, nslots * Wl, nslots * Wl, nslots * Wl};
+          } else {
+            valid = FULL || bpx >= 0;
+            bpx = valid ? bpx : 0;
+          }
           f4 zf[NBY];
 #pragma unroll
           for (int b2 = 0; b2 < NBY; ++b2) {
-            const float* dp = d_s + bpx * PPY + rsy + PPY + 16 * b2 + c16;
-            float y00 = dp[0], y01 = dp[PPY], y10 = dp[rsy], y11 = dp[rsy + PPY];
+            const float* dp = d_s + PPY + 16 * b2 + c16;
+            const int o1 = row_off(bpx, 1, PPY), o2 = row_off(bpx, 2, PPY);
+            float y00 = dp[o1], y01 = dp[o1 + PPY], y10 = dp[o2], y11 = dp[o2 + PPY];
             if (!FULL && !valid) y00 = y01 = y10 = y11 = 0.f;
             if constexpr (AR == 0) dbacc[b2] += (y00 + y01) + (y10 + y11);
             float r0, r1;
@@ -2430,14 +2644,15 @@ __global__ __launch_bounds__(512, 2) void wino_bwd_fused32_kernel(WinoBwdArgs a)
           }
 #pragma unroll
           for (int b = 0; b < NBX; ++b) {
-            const float* xp = x_s + bpx * PPX + 16 * b + c16;
+            const float* xp = x_s + 16 * b + c16;
             // the two patch rows B^T row AR combines
             constexpr int RA = AR == 0 ? 0 : 1;
             constexpr int RB = AR == 3 ? 3 : 2;
+            const int oa = row_off(bpx, RA, PPX), ob = row_off(bpx, RB, PPX);
             float ra[4], rb[4];
 #pragma unroll
             for (int dx = 0; dx < 4; ++dx) {
-              float u = xp[RA * rsx + dx * PPX], w = xp[RB * rsx + dx * PPX];
+              float u = xp[oa + dx * PPX], w = xp[ob + dx * PPX];
               if constexpr (RELU) {
                 u = relu0(u);
                 w = relu0(w);
@@ -2569,9 +2784,28 @@ bool run_wino_bwd32_g(const float* dy, const float* w, const float* x, const flo
   a.fault = g_wino_fault;
   static const int fprio = measure_knob("SA_FUSED_PRIO", 0);
   a.prio = fprio;
-  auto kern = wino_bwd_fused32_kernel<CX, CY, RT, MAXCX, MAXCY, RELU, MASK, GH, GW>;
-  allow_lds_w(kern, bytes);
-  hipLaunchKernelGGL(kern, dim3(G), dim3(512), bytes, s, a);
+  // the row-keeping stager, where its tables fit and no range that shares
+  // rows with its predecessor needs a second chunk (else the plain stager).
+  // Declined: maps whose ranges are whole tile rows of one image, which use
+  // all maxrows rows for image rows and leave none for the zero row (the
+  // Doom ladder's 36x64; 16x48), and any instance whose extra tables would
+  // pass 160 KB of LDS (none of the compile-time maps).
+  // conv_wino_keep_launches() counts the launches that kept rows.
+  constexpr int KCX = fused32_keep_slots(CX, CY, false), KCY = fused32_keep_slots(CX, CY, true);
+  const int krows = std::min({KCY * 512 / (Wl * (CY / 4)), KCX * 512 / (Wl * (CX / 4)),
+                              maxrows - 1});
+  const size_t kbytes = bytes + fused32_keep_lds(RT, maxrows);
+  if (wino_keep_enabled() && kbytes <= 160 * 1024 &&
+      fused32_keep_fits(RT, H, TX, TY, NT, nranges, maxrows, krows)) {
+    auto kern = wino_bwd_fused32_kernel<CX, CY, RT, KCX, KCY, RELU, MASK, GH, GW, true>;
+    allow_lds_w(kern, kbytes);
+    hipLaunchKernelGGL(kern, dim3(G), dim3(512), kbytes, s, a);
+    ++g_wino_keep_launches;
+  } else {
+    auto kern = wino_bwd_fused32_kernel<CX, CY, RT, MAXCX, MAXCY, RELU, MASK, GH, GW>;
+    allow_lds_w(kern, bytes);
+    hipLaunchKernelGGL(kern, dim3(G), dim3(512), bytes, s, a);
+  }
   wgrad_reduce_slots(ws, G, rows16, CY, CX, dw, db, s);
   return true;
 }
@@ -2924,6 +3158,14 @@ int conv_wino_geo(int v) {
   if (v == 0 || v == 1) g_wino_geo = v;
   return old;
 }
+
+int conv_wino_keep(int v) {
+  const int old = wino_keep_enabled() ? 1 : 0;
+  if (v == 0 || v == 1) g_wino_keep = v;
+  return old;
+}
+
+int64_t conv_wino_keep_launches() { return g_wino_keep_launches; }
 
 bool wino_enabled() {
   static const bool on = env_knob("SA_F32_WINO", 1) != 0;

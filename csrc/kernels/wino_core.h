@@ -29,6 +29,7 @@ namespace cf32 {
 namespace wino {
 
 typedef float f4 __attribute__((ext_vector_type(4)));
+typedef int i4 __attribute__((ext_vector_type(4)));
 
 // Measurement knobs (SA_WINO_ABLATE / SA_FUSED_ABLATE: drop parts of a
 // kernel's work to time the rest) exist only in builds with
