@@ -7,6 +7,7 @@
 #include <cstdlib>
 #include <climits>
 #include <algorithm>
+#include <array>
 #include <c10/hip/HIPStream.h>
 #include <c10/core/DeviceGuard.h>
 
@@ -432,6 +433,72 @@ std::vector<at::Tensor> res_block_fwd(at::Tensor x, at::Tensor w1, at::Tensor b1
   return {y};
 }
 
+// The last stage of the deep torso (actor inference) in one launch
+// (conv_wino.hip wino_stage_tail_kernel).  head == nullptr: both residual
+// blocks of x [N,H,W,32], bitwise two cf32_res_block_fwd; else x is the
+// stage's input [N,18,24,32] and the head (conv + bias + max-pool) runs in
+// the same launch, bitwise cf32_wino_conv_pool_fwd followed by the blocks.
+// {} when the shape is not covered (nothing ran).
+std::vector<at::Tensor> stage_fwd_impl(const char* what, at::Tensor x, const at::Tensor* head_w,
+                                       const at::Tensor* head_b,
+                                       const std::array<at::Tensor, 8>& p, bool last) {
+  check_nhwc(x, "x");
+  TORCH_CHECK(x.scalar_type() == at::kFloat, "x must be float32");
+  const int64_t C = x.size(3);
+  const float* w[4];
+  const float* b[4];
+  for (int i = 0; i < 4 + (head_w ? 1 : 0); ++i) {
+    const at::Tensor& wt = i < 4 ? p[2 * i] : *head_w;
+    const at::Tensor& bt = i < 4 ? p[2 * i + 1] : *head_b;
+    check_w(wt);
+    TORCH_CHECK(wt.size(0) == 3 && wt.size(2) == C && wt.size(3) == C, what,
+                ": HWIO [3,3,C,C] weights for a C-channel map");
+    TORCH_CHECK(bt.is_cuda() && bt.scalar_type() == at::kFloat && bt.is_contiguous() &&
+                    bt.numel() == C, "bias");
+    if (i < 4) {
+      w[i] = wt.data_ptr<float>();
+      b[i] = bt.data_ptr<float>();
+    }
+  }
+  if (C != 32 || x.size(0) > sa::cf32::kResBlockMaxFrames || x.size(1) > INT_MAX ||
+      x.size(2) > INT_MAX)
+    return {};
+  const c10::DeviceGuard g(x.device());
+  const int N = static_cast<int>(x.size(0)), H = static_cast<int>(x.size(1)),
+            W = static_cast<int>(x.size(2));
+  at::Tensor y;
+  if (head_w) {
+    if (H % 2 != 0 || W % 2 != 0) return {};
+    y = at::empty({N, H / 2, W / 2, C}, x.options());
+    if (!sa::cf32::wino_stage_launch(x.data_ptr<float>(), head_w->data_ptr<float>(),
+                                     head_b->data_ptr<float>(), w, b, y.data_ptr<float>(), N,
+                                     H, W, static_cast<int>(C), last, stream()))
+      return {};
+  } else {
+    y = at::empty(x.sizes(), x.options());
+    if (!sa::cf32::wino_stage_tail_launch(x.data_ptr<float>(), w, b, y.data_ptr<float>(), N, H,
+                                          W, static_cast<int>(C), last, stream()))
+      return {};
+  }
+  check_launch(what);
+  return {y};
+}
+
+std::vector<at::Tensor> stage_tail_fwd(at::Tensor x, at::Tensor w1a, at::Tensor b1a,
+                                       at::Tensor w2a, at::Tensor b2a, at::Tensor w1b,
+                                       at::Tensor b1b, at::Tensor w2b, at::Tensor b2b, bool last) {
+  return stage_fwd_impl("cf32_stage_tail_fwd", x, nullptr, nullptr,
+                        {w1a, b1a, w2a, b2a, w1b, b1b, w2b, b2b}, last);
+}
+
+std::vector<at::Tensor> stage_fwd(at::Tensor x, at::Tensor w_head, at::Tensor b_head,
+                                  at::Tensor w1a, at::Tensor b1a, at::Tensor w2a, at::Tensor b2a,
+                                  at::Tensor w1b, at::Tensor b1b, at::Tensor w2b, at::Tensor b2b,
+                                  bool last) {
+  return stage_fwd_impl("cf32_stage_fwd", x, &w_head, &b_head,
+                        {w1a, b1a, w2a, b2a, w1b, b1b, w2b, b2b}, last);
+}
+
 std::vector<at::Tensor> maxpool_fwd(at::Tensor x, int64_t pb_h, int64_t pb_w) {
   check_nhwc(x, "x");
   TORCH_CHECK(x.scalar_type() == at::kFloat && x.size(3) % 4 == 0, "maxpool: float32, C % 4 == 0");
@@ -509,6 +576,16 @@ void register_conv_f32_ops(pybind11::module& m) {
         arg("stages") = -1);
   m.def("cf32_res_block_fwd", &res_block_fwd, arg("x"), arg("w1"), arg("b1"), arg("w2"),
         arg("b2"), arg("last") = false);
+  m.def("cf32_stage_tail_fwd", &stage_tail_fwd, arg("x"), arg("w1a"), arg("b1a"), arg("w2a"),
+        arg("b2a"), arg("w1b"), arg("b1b"), arg("w2b"), arg("b2b"), arg("last") = false);
+  m.def("cf32_stage_fwd", &stage_fwd, arg("x_in"), arg("w_head"), arg("b_head"), arg("w1a"),
+        arg("b1a"), arg("w2a"), arg("b2a"), arg("w1b"), arg("b1b"), arg("w2b"), arg("b2b"),
+        arg("last") = false);
+  // which of the two takes a last stage whose input is N x [H, W, C]: 2 the
+  // whole stage (cf32_stage_fwd), 1 the tail after the head's own launches
+  // (cf32_stage_tail_fwd), 0 neither
+  m.def("cf32_stage_form",
+        [](int N, int H, int W, int C) { return sa::cf32::wino_stage_form(N, H, W, C); });
   // output rows per workgroup of cf32_res_block_fwd for a C-channel map of
   // width W (0: no instance); tests cross every band seam with it
   m.def("cf32_res_block_band", [](int C, int W) { return sa::cf32::wino_res_block_band(C, W); });

@@ -134,6 +134,29 @@ int wino_res_block_band(int C, int W);
 bool wino_res_block_launch(const float* x, const float* w1, const float* b1, const float* w2,
                            const float* b2, float* y, int N, int H, int W, int C, bool last,
                            hipStream_t s);
+// The last stage of the deep torso for actor inference in one launch, one
+// workgroup per image (conv_wino.hip wino_stage_tail_kernel), C = 32, fp32
+// NHWC, w / b = {conv1a, conv2a, conv1b, conv2b}:
+//   wino_stage_tail_launch  both residual blocks of a stage whose whole map
+//                           fits in LDS beside U (9x12, 11x11, 9x16), x', t
+//                           only in LDS; bitwise two wino_res_block_launch
+//   wino_stage_launch       x [N,18,24,32]: the stage head (conv + bias +
+//                           3x3/2 SAME max-pool, no argmax) and both blocks,
+//                           y [N,9,12,32]; bitwise wino_conv_pool_launch
+//                           followed by the tail
+// False (nothing launched) where any conv replaced would not run the Winograd
+// forward, where the head is not the whole-image conv + pool, where the LDS
+// does not fit, for C != 32 or above kResBlockMaxFrames images.
+bool wino_stage_tail_launch(const float* x, const float* const* w,
+                            const float* const* b, float* y, int N, int H, int W, int C,
+                            bool last, hipStream_t s);
+bool wino_stage_launch(const float* x, const float* wh, const float* bh,
+                       const float* const* w, const float* const* b, float* y, int N,
+                       int H, int W, int C, bool last, hipStream_t s);
+// Which of the two takes a last stage whose INPUT is N x [H, W, C]: 2 the
+// whole stage, 1 the tail (after the head's own launches), 0 neither.  Host
+// arithmetic only.
+int wino_stage_form(int N, int H, int W, int C);
 // Stage head with the 3x3/2 SAME max-pool fused (conv_wino.hip): x [N,H,W,Cin]
 // -> pooled [N,H/2,W/2,Cout] + argmax codes, the 3x3/1 conv + bias in
 // Winograd form, the pre-pool map only in LDS.  (Cin, Cout) = (16, 32) with

@@ -34,8 +34,8 @@
 //
 // The device utilities and one set of phase functions (weight, input and
 // output transforms, the MFMA block, the register-prefetch stager) are in
-// wino_core.h.  The stage-head kernels and the residual block are built from
-// them alone; wino_conv_kernel calls them for the weight transform, the
+// wino_core.h.  The stage-head kernels, the residual block and the one-launch
+// last stage are built from them alone; wino_conv_kernel calls them for the weight transform, the
 // stager and the input / output transforms, the two fused backward kernels
 // for the weight transform and the slot tables; each kernel that keeps text
 // of its own says why.
@@ -1137,6 +1137,23 @@ struct PoolImgGeo {
   static constexpr size_t bytes = sizeof(float) * (16 * CIN * COUT + XREG + ROWS);
 };
 
+// The 3x3 / 2 window of pooled element (pr, pc), channel quad pq, over a whole
+// pre-pool LDS image [H][W][IPP] (pad-before 0: the tap row / column past the
+// map is padding), taps in row-major order
+template <int H, int W, int IPP>
+__device__ __forceinline__ void pool_window_img(const float* img, int pr, int pc, int pq, f4& best,
+                                                int (&code)[4]) {
+#pragma unroll
+  for (int dy = 0; dy < 3; ++dy)
+#pragma unroll
+    for (int dx = 0; dx < 3; ++dx) {
+      const int y = 2 * pr + dy, x = 2 * pc + dx;
+      if (y < H && x < W)
+        pool_take(best, code, *reinterpret_cast<const f4*>(img + (y * W + x) * IPP + 4 * pq),
+                  3 * dy + dx);
+    }
+}
+
 template <int CIN, int COUT, int H, int W>
 __global__ __launch_bounds__(512, 1) void wino_conv_pool_img_kernel(WinoPoolArgs pa) {
   using P = PoolImgGeo<CIN, COUT, H, W>;
@@ -1265,6 +1282,8 @@ __global__ __launch_bounds__(512, 1) void wino_conv_pool_img_kernel(WinoPoolArgs
       const int pc = rem / CQ, pq = rem - pc * CQ;
       f4 best = {kNegInf, kNegInf, kNegInf, kNegInf};
       int code[4] = {0, 0, 0, 0};
+      // (own text: through pool_window_img this kernel's instruction stream
+      // changed, profiles/experiments.md)
 #pragma unroll
       for (int dy = 0; dy < 3; ++dy)
 #pragma unroll
@@ -1287,6 +1306,7 @@ bool run_wino_pool_img(const float* x, const float* w, const float* b, float* po
                        uint8_t* arg, int N, int Hr, int Wr, hipStream_t s) {
   using P = PoolImgGeo<CIN, COUT, H, W>;
   if (Hr != H || Wr != W || static_cast<int64_t>(N) * H * W * CIN * 4 > kMaxBufBytes) return false;
+  if (t_wino_probe) return true;  // wino_stage_launch asks whether this head runs
   WinoArgs a{};
   a.src = x;
   a.w = w;
@@ -3090,6 +3110,299 @@ bool run_res_block(const ResBlockArgs& a, hipStream_t s) {
   return true;
 }
 
+// ------------------------------------------------- fused last stage
+// The deep torso's last stage for actor inference, one workgroup per image:
+// both residual blocks of a 32-channel stage whose WHOLE map fits in LDS
+// (9x12, 11x11, 9x16: the last maps of the three frame ladders),
+//   t  = relu(conv1a(relu(x)) + b1a);   x' = conv2a(t) + b2a + x
+//   t  = relu(conv1b(relu(x')) + b1b);  y  = conv2b(t) + b2b + x'  [then relu]
+// with x, x' and t only in LDS.  No band, so no halo: conv1 is computed once
+// per tile, each weight tensor is transformed once per image (into the one U
+// buffer, between barriers), and the map never visits HBM between the four
+// convs.  The x and t images are [2 TY + 2][2 TX + 2][C + 4] with image pixel
+// (y, x) at (y + 1, x + 1); everything outside the image stays zero (conv2's
+// SAME padding pads t, conv1b's pads x'): only cells inside the image are
+// ever written, which also keeps the row / column an odd map's last tiles
+// overhang at zero.  x' is written over x by the lane that read x there as
+// its residual operand (raw, not ReLU'd: conv1 applies the ReLU when it loads
+// a patch), so that write needs no barrier of its own.
+//
+// HEAD (the 18x24 -> 9x12 stage of the 72x96 frame): the stage head's conv and
+// 3x3 / 2 max-pool run first in the same workgroup, as in
+// wino_conv_pool_img_kernel: the staged input (75 KB), then the pre-pool map
+// over it.  U, that region and an x image do not fit in 160 KB together, so a
+// thread holds its (at most two) pooled float4s in registers across the
+// barrier that ends the pool's reads, and the x and t images then take the
+// region's place.  No argmax: inference keeps nothing for a backward.
+//
+// Per output element the arithmetic is that of the launches replaced: the
+// same transforms, wino_mfma_block's k-step order, bias - residual - ReLU,
+// strict > over row-major taps (tests/test_stage_fused_f32_gpu.py: bitwise).
+struct StageArgs {
+  const float* x;     // [N, H, W, C]; HEAD: the head's input [N, 18, 24, C]
+  const float* wh;    // HEAD: the head's weights HWIO [3, 3, C, C] and bias
+  const float* bh;
+  const float* w[4];  // conv1a, conv2a, conv1b, conv2b: HWIO [3, 3, C, C]
+  const float* b[4];  // [C]
+  float* y;           // [N, H, W, C]
+  int N, H, W, TY, TX, last;  // the residual map and its tile grid
+  float rTX, rWl;
+};
+
+// Rows of image n (raw, [H][W][C] in a buffer of N images) into an LDS image
+// [rows][Wl][C + 4], pixel (y, x) at (y + 1, x + 1), zeros around it (a
+// buffer load past the end returns zeros: the padding needs no select)
+template <int C, int NTH>
+__device__ __forceinline__ void stage_whole_image(float* img, const float* src, int N, int n,
+                                                  int H, int W, int rows, int Wl, float rWl) {
+  constexpr int PP = C + 4, C4 = C / 4, LC4 = C4 == 4 ? 2 : 3, KB = 4;
+  const auto srcr = buf_rsrc(src, static_cast<int64_t>(N) * H * W * C);
+  const int nx = rows * Wl * C4;
+  for (int e0 = threadIdx.x; e0 < nx; e0 += KB * NTH) {
+    f4 stg[KB];
+#pragma unroll
+    for (int k = 0; k < KB; ++k) {
+      const int e = e0 + k * NTH;
+      const int ch = e & (C4 - 1), pix = e >> LC4;
+      const int L = fdivi(pix, rWl), col = pix - L * Wl;
+      const int y = L - 1, xc = col - 1;
+      const bool in = e < nx && y >= 0 && y < H && xc >= 0 && xc < W;
+      stg[k] = bload(srcr, in ? static_cast<uint32_t>(((n * H + y) * W + xc) * C + 4 * ch) * 4u
+                              : kOOB);
+    }
+#pragma unroll
+    for (int k = 0; k < KB; ++k) {
+      const int e = e0 + k * NTH;
+      if (e < nx) *reinterpret_cast<f4*>(img + (e >> LC4) * PP + 4 * (e & (C4 - 1))) = stg[k];
+    }
+  }
+}
+
+// One conv over a whole LDS image: the (16 tiles x 16 output channels) tasks
+// of the TY x TX tile grid over the workgroup's NW waves; epi(ty, tx, co, Y)
+// gets a lane's 2x2 outputs of 4 channels (only for tiles of the grid)
+template <int C, int NW, bool RELU, typename Epi>
+__device__ __forceinline__ void stage_conv(const float* img, const float* U_s, int TY, int TX,
+                                           float rTX, int Wl, Epi epi) {
+  constexpr int PP = C + 4, NS = C / 16;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int g = lane >> 4, c16 = lane & 15;
+  const int nt = TY * TX, ng = (nt + 15) >> 4;
+  for (int task = wave; task < ng * NS; task += NW) {
+    const int sl = task / ng, grp = task - sl * ng;
+    const int co0 = 16 * sl;
+    int t = 16 * grp + c16;
+    const bool valid = t < nt;
+    if (!valid) t = 0;
+    const int ty = fdivi(t, rTX), tx = t - ty * TX;
+    const F4x4 Ys = res_tile<C, RELU>(img + (2 * ty * Wl + 2 * tx) * PP + 4 * g, Wl * PP,
+                                      U_s + (g * C + co0 + c16) * 4);
+    if (valid) epi(ty, tx, co0 + 4 * g, Ys);
+  }
+}
+
+template <int C, bool HEAD>
+constexpr size_t stage_tail_bytes(int TY, int TX) {
+  const size_t imgs = static_cast<size_t>(2) * (2 * TY + 2) * (2 * TX + 2) * (C + 4);
+  const size_t head = HEAD ? PoolImgGeo<C, C, 18, 24>::XREG : 0;
+  return sizeof(float) * (16 * C * C + (imgs > head ? imgs : head));
+}
+
+template <int C, bool HEAD = false>
+__global__ __launch_bounds__(512, 1) void wino_stage_tail_kernel(StageArgs a) {
+  constexpr int NW = 8, NTH = 64 * NW, PP = C + 4, C4 = C / 4;
+  static_assert(C == 32, "C");
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  const int Wl = 2 * a.TX + 2, IH = 2 * a.TY + 2, rowstr = Wl * PP;
+  float* U_s = smem;               // [16 xi][C/16][4 g][C][4]
+  float* x_s = smem + 16 * C * C;  // [IH][Wl][PP]: x, then x'
+  float* t_s = x_s + IH * rowstr;  // [IH][Wl][PP]
+  const int n = blockIdx.x;
+
+  auto u_transform = [&](const float* __restrict__ w) __attribute__((always_inline)) {
+    wino_u_to_lds<C / 16, C, NTH>(U_s, C * C, [&](int ky, int kx, int ci, int co) {
+      return w[((ky * 3 + kx) * C + ci) * C + co];
+    });
+  };
+  auto zero_t = [&]() __attribute__((always_inline)) {
+    for (int e = threadIdx.x; e < IH * rowstr / 4; e += NTH)
+      reinterpret_cast<f4*>(t_s)[e] = f4{0.f, 0.f, 0.f, 0.f};
+  };
+
+  if constexpr (HEAD) {
+    // ---- the stage head: conv + bias over the staged 18x24 input, the
+    // pre-pool map over it, the pooled map into registers
+    using P = PoolImgGeo<C, C, 18, 24>;
+    constexpr int HH = 18, HW = 24, HWl = P::Wl, hrow = HWl * PP, IPP = P::IPP;
+    constexpr int Hp = HH / 2, Wp = HW / 2, CQ = C / 4;
+    static_assert(P::NW == NW && P::NTASK <= 2 * NW && Hp * Wp * CQ <= 2 * NTH, "head");
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int g = lane >> 4, c16 = lane & 15;
+    float* img = x_s;  // [HH][HW][IPP], over the staged rows
+    u_transform(a.wh);
+    stage_whole_image<C, NTH>(x_s, a.x, a.N, n, HH, HW, P::ROWS, HWl, 1.f / HWl);
+    __syncthreads();
+    f4 Yt[2][4];
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      const int task = wave + NW * i;
+      const int grp = task % P::NG, sl = task / P::NG;
+      const int t0 = 16 * grp + c16;
+      const int t = t0 < P::NTI ? t0 : 0;
+      const int ty = t / P::TX, tx = t - ty * P::TX;
+#pragma unroll
+      for (int q = 0; q < 4; ++q) Yt[i][q] = f4{0.f, 0.f, 0.f, 0.f};
+      if (task < P::NTASK) {
+        const F4x4 Ys = wino_tile<C / 16, false, false>(
+            x_s + (2 * ty * HWl + 2 * tx) * PP + 4 * g, hrow, PP,
+            U_s + (g * C + 16 * sl + c16) * 4, C * C, 4 * C * 4);
+        const f4 bv = *reinterpret_cast<const f4*>(a.bh + 16 * sl + 4 * g);
+#pragma unroll
+        for (int q = 0; q < 4; ++q) Yt[i][q] = Ys.v[q] + bv;
+      }
+    }
+    __syncthreads();  // every wave's patch reads are done: the region becomes the image
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      const int task = wave + NW * i;
+      const int grp = task % P::NG, sl = task / P::NG;
+      const int t = 16 * grp + c16;
+      if (task < P::NTASK && t < P::NTI) {
+        const int ty = t / P::TX, tx = t - ty * P::TX;
+#pragma unroll
+        for (int dy = 0; dy < 2; ++dy)
+#pragma unroll
+          for (int dx = 0; dx < 2; ++dx)
+            *reinterpret_cast<f4*>(img + ((2 * ty + dy) * HW + 2 * tx + dx) * IPP + sl * 16 +
+                                   4 * g) = Yt[i][2 * dy + dx];
+      }
+    }
+    __syncthreads();
+    constexpr float kNegInf = -__builtin_inff();
+    constexpr PoolLaneMap<CQ, IPP> kMap{};
+    const int lmap = kMap.pj[lane] * CQ + kMap.pq[lane];
+    f4 pooled[2];
+    int pcell[2];  // the item's float offset in the x image, -1: none
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+      const int e = (threadIdx.x & ~63) + k * NTH + lmap;
+      pooled[k] = f4{kNegInf, kNegInf, kNegInf, kNegInf};
+      pcell[k] = -1;
+      if (e < Hp * Wp * CQ) {
+        const int pr = e / (Wp * CQ), rem = e - pr * (Wp * CQ);
+        const int pc = rem / CQ, pq = rem - pc * CQ;
+        int code[4] = {0, 0, 0, 0};
+        pool_window_img<HH, HW, IPP>(img, pr, pc, pq, pooled[k], code);
+        pcell[k] = ((pr + 1) * Wl + pc + 1) * PP + 4 * pq;
+      }
+    }
+    __syncthreads();  // the pool's reads are done: the region becomes the x and t images
+#pragma unroll
+    for (int k = 0; k < 2; ++k)
+      if (pcell[k] >= 0) *reinterpret_cast<f4*>(x_s + pcell[k]) = pooled[k];
+    for (int e = threadIdx.x; e < IH * Wl * C4; e += NTH) {  // x's zero border
+      const int pix = e / C4, r = fdivi(pix, a.rWl), c = pix - r * Wl;
+      if (r < 1 || r > a.H || c < 1 || c > a.W)
+        *reinterpret_cast<f4*>(x_s + pix * PP + 4 * (e % C4)) = f4{0.f, 0.f, 0.f, 0.f};
+    }
+    zero_t();
+  } else {
+    stage_whole_image<C, NTH>(x_s, a.x, a.N, n, a.H, a.W, IH, Wl, a.rWl);
+    zero_t();
+  }
+  u_transform(a.w[0]);
+  __syncthreads();
+
+#pragma unroll 1
+  for (int blk = 0; blk < 2; ++blk) {
+    const float* w1 = blk ? a.w[2] : a.w[0];
+    const float* w2 = blk ? a.w[3] : a.w[1];
+    const float* b1 = blk ? a.b[2] : a.b[0];
+    const float* b2 = blk ? a.b[3] : a.b[1];
+    if (blk) {
+      __syncthreads();  // x' complete, every wave done with t and conv2a's U
+      u_transform(w1);
+      __syncthreads();
+    }
+    // ---- conv1: t = relu(conv(relu(x)) + b1) inside the image
+    stage_conv<C, NW, true>(x_s, U_s, a.TY, a.TX, a.rTX, Wl,
+                            [&](int ty, int tx, int co, const F4x4& Ys) {
+      const f4 bv = *reinterpret_cast<const f4*>(b1 + co);
+#pragma unroll
+      for (int dy = 0; dy < 2; ++dy)
+#pragma unroll
+        for (int dx = 0; dx < 2; ++dx) {
+          const int oy = 2 * ty + dy, ox = 2 * tx + dx;
+          if (oy >= a.H || ox >= a.W) continue;  // t stays zero there
+          f4 v = Ys.v[2 * dy + dx] + bv;
+#pragma unroll
+          for (int k = 0; k < 4; ++k) v[k] = relu0(v[k]);
+          *reinterpret_cast<f4*>(t_s + ((oy + 1) * Wl + ox + 1) * PP + co) = v;
+        }
+    });
+    __syncthreads();  // t complete, every wave done with w1's U
+    u_transform(w2);
+    __syncthreads();
+    // ---- conv2: conv(t) + b2 + x, over x in LDS (first block) or to HBM
+    stage_conv<C, NW, false>(t_s, U_s, a.TY, a.TX, a.rTX, Wl,
+                             [&](int ty, int tx, int co, const F4x4& Ys) {
+      const f4 bv = *reinterpret_cast<const f4*>(b2 + co);
+#pragma unroll
+      for (int dy = 0; dy < 2; ++dy)
+#pragma unroll
+        for (int dx = 0; dx < 2; ++dx) {
+          const int oy = 2 * ty + dy, ox = 2 * tx + dx;
+          if (oy >= a.H || ox >= a.W) continue;  // x' stays zero there
+          f4* xc = reinterpret_cast<f4*>(x_s + ((oy + 1) * Wl + ox + 1) * PP + co);
+          f4 v = Ys.v[2 * dy + dx] + bv;
+          v += *xc;
+          if (blk == 0) {
+            *xc = v;
+            continue;
+          }
+          if (a.last) {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) v[k] = relu0(v[k]);
+          }
+          const int64_t o = ((static_cast<int64_t>(n) * a.H + oy) * a.W + ox) * C + co;
+          *reinterpret_cast<f4*>(a.y + o) = v;
+        }
+    });
+  }
+}
+
+template <bool HEAD>
+bool run_stage_tail(const StageArgs& a, hipStream_t s) {
+  const size_t bytes = stage_tail_bytes<32, HEAD>(a.TY, a.TX);
+  if (bytes > 160 * 1024) return false;
+  auto kern = wino_stage_tail_kernel<32, HEAD>;
+  allow_lds_w(kern, bytes);
+  hipLaunchKernelGGL(kern, dim3(a.N), dim3(512), bytes, s, a);
+  return true;
+}
+
+// Whether both convs of a residual block at this shape run the Winograd
+// forward (the direct kernel they would fall to sums in another order);
+// launches nothing
+bool res_convs_take_wino(const float* x, const float* w1, const float* b1, const float* w2,
+                         const float* b2, float* y, int N, int H, int W, int C, bool last,
+                         hipStream_t s) {
+  ConvArgs c{};
+  c.src = x; c.w = w1; c.bias = b1; c.out = y;
+  c.N = N; c.Hs = H; c.Ws = W; c.Cs = C;
+  c.Ho = H; c.Wo = W; c.Cout = C;
+  c.pt = 1; c.pl = 1; c.D = 1;
+  c.wcin = C; c.wcout = C;
+  c.relu_in = 1; c.relu_out = 1;
+  t_wino_probe = true;
+  bool both = wino_conv_launch(c, false, s);
+  c.w = w2; c.bias = b2; c.add = x;
+  c.relu_in = 0; c.relu_out = last ? 1 : 0;
+  both = both && wino_conv_launch(c, false, s);
+  t_wino_probe = false;
+  return both;
+}
+
 }  // namespace
 
 // Band heights (output rows per workgroup) of the fused residual block: per
@@ -3118,20 +3431,7 @@ bool wino_res_block_launch(const float* x, const float* w1, const float* b1, con
   if (R == 0) return false;
   // the two launches this replaces must both run the Winograd forward (the
   // direct kernel they would fall to sums in another order)
-  ConvArgs c{};
-  c.src = x; c.w = w1; c.bias = b1; c.out = y;
-  c.N = N; c.Hs = H; c.Ws = W; c.Cs = C;
-  c.Ho = H; c.Wo = W; c.Cout = C;
-  c.pt = 1; c.pl = 1; c.D = 1;
-  c.wcin = C; c.wcout = C;
-  c.relu_in = 1; c.relu_out = 1;
-  t_wino_probe = true;
-  bool both = wino_conv_launch(c, false, s);
-  c.w = w2; c.bias = b2; c.add = x;
-  c.relu_in = 0; c.relu_out = last ? 1 : 0;
-  both = both && wino_conv_launch(c, false, s);
-  t_wino_probe = false;
-  if (!both) return false;
+  if (!res_convs_take_wino(x, w1, b1, w2, b2, y, N, H, W, C, last, s)) return false;
   ResBlockArgs a{};
   a.x = x; a.w1 = w1; a.b1 = b1; a.w2 = w2; a.b2 = b2; a.y = y;
   a.N = N; a.H = H; a.W = W;
@@ -3145,6 +3445,76 @@ bool wino_res_block_launch(const float* x, const float* w1, const float* b1, con
   }
   if (R == 6) return run_res_block<32, 6, 8>(a, s);
   return run_res_block<32, 4, 8>(a, s);
+}
+
+namespace {
+
+// the checks both stage launchers share; fills the residual map's geometry
+bool stage_tail_args(StageArgs& a, const float* const* w, const float* const* b,
+                     float* y, int N, int H, int W, int C, bool last, hipStream_t s) {
+  if (N < 1 || N > kResBlockMaxFrames || C != 32 || H < 1 || W < 1 || !wino_enabled())
+    return false;
+  a.TY = (H + 1) / 2; a.TX = (W + 1) / 2;
+  if (a.TY > 1024 || a.TX > 1024 || stage_tail_bytes<32, false>(a.TY, a.TX) > 160 * 1024)
+    return false;
+  // each of the four launches this replaces must run the Winograd forward;
+  // the first block never applies the torso's final ReLU
+  if (!res_convs_take_wino(y, w[0], b[0], w[1], b[1], y, N, H, W, C, false, s) ||
+      !res_convs_take_wino(y, w[2], b[2], w[3], b[3], y, N, H, W, C, last, s))
+    return false;
+  for (int i = 0; i < 4; ++i) {
+    a.w[i] = w[i];
+    a.b[i] = b[i];
+  }
+  a.y = y;
+  a.N = N; a.H = H; a.W = W;
+  a.last = last ? 1 : 0;
+  a.rTX = 1.f / static_cast<float>(a.TX);
+  a.rWl = 1.f / static_cast<float>(2 * a.TX + 2);
+  return true;
+}
+
+}  // namespace
+
+bool wino_stage_tail_launch(const float* x, const float* const* w,
+                            const float* const* b, float* y, int N, int H, int W, int C,
+                            bool last, hipStream_t s) {
+  StageArgs a{};
+  if (!stage_tail_args(a, w, b, y, N, H, W, C, last, s)) return false;
+  a.x = x;
+  return run_stage_tail<false>(a, s);
+}
+
+bool wino_stage_launch(const float* x, const float* wh, const float* bh,
+                       const float* const* w, const float* const* b, float* y, int N,
+                       int H, int W, int C, bool last, hipStream_t s) {
+  // the head this replaces must be the whole-image Winograd conv + pool
+  if (H != 18 || W != 24 || C != 32 || N < 1 || N > kResBlockMaxFrames) return false;
+  t_wino_probe = true;
+  const bool head = wino_conv_pool_launch(x, wh, bh, y, nullptr, nullptr, 0, N, H, W, C, C, -1, s);
+  t_wino_probe = false;
+  StageArgs a{};
+  if (!head || !stage_tail_args(a, w, b, y, N, H / 2, W / 2, C, last, s)) return false;
+  a.x = x; a.wh = wh; a.bh = bh;
+  return run_stage_tail<true>(a, s);
+}
+
+int wino_stage_form(int N, int H, int W, int C) {
+  static const float dummy[4] = {};
+  float* y = const_cast<float*>(dummy);  // geometry checks only: never read or written
+  const float* const w[4] = {dummy, dummy, dummy, dummy};
+  if (H == 18 && W == 24 && C == 32 && N >= 1 && N <= kResBlockMaxFrames) {
+    t_wino_probe = true;
+    const bool head = wino_conv_pool_launch(dummy, dummy, dummy, y, nullptr, nullptr, 0, N, H, W,
+                                            C, C, -1, nullptr);
+    t_wino_probe = false;
+    StageArgs a{};
+    if (head && stage_tail_args(a, w, w, y, N, H / 2, W / 2, C, true, nullptr) &&
+        stage_tail_bytes<32, true>(a.TY, a.TX) <= 160 * 1024)
+      return 2;
+  }
+  StageArgs a{};
+  return stage_tail_args(a, w, w, y, N, (H + 1) / 2, (W + 1) / 2, C, true, nullptr) ? 1 : 0;
 }
 
 int conv_wino_fault(int v) {

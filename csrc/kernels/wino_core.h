@@ -1,6 +1,7 @@
 // The Winograd F(2x2, 3x3) phases shared by the fp32 conv kernels of
-// conv_wino.hip, and their device utilities.  The two fused stage heads and
-// the fused residual block are built from these functions alone; the
+// conv_wino.hip, and their device utilities.  The two fused stage heads, the
+// fused residual block and the one-launch last stage are built from these
+// functions alone; the
 // forward / data-gradient kernel calls the weight transform, the stager and
 // the input / output transforms; the two fused backward kernels the weight
 // transform and the slot tables.  Where a kernel keeps text of its own, a

@@ -161,10 +161,21 @@ def _log_torso_blocks(flags, model):
   """Which form the inference model's residual blocks run (--torso_blocks)."""
   asked = getattr(flags, 'torso_blocks', 'ops')
   used = model.torso_blocks
+  agent = model.agent
+  if asked == used == 'stage':
+    form = agent.torso_stage_form(model.device.type == 'cuda')
+    log.info('actor inference torso blocks: stage (%s in one launch)',
+             'the last stage: head, max-pool and both blocks'
+             if form == 'stage' else 'the two blocks of the last stage')
+    return
   if asked == used:
     log.info('actor inference torso blocks: %s', used)
     return
-  agent = model.agent
+  if asked == 'stage' and used == 'fused':
+    log.info('actor inference torso blocks: fused (--torso_blocks=stage: the '
+             'stage kernel does not take the last map of %s frames)',
+             'x'.join(str(d) for d in agent.frame_shape))
+    return
   if getattr(agent, 'backend', 'torch') != 'hip' or model.device.type != 'cuda':
     why = 'the torch backend has no block kernel'
   elif agent.torso_kind != 'deep':

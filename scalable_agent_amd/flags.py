@@ -116,13 +116,18 @@ def build_parser() -> argparse.ArgumentParser:
                       'packs the outputs).  Both take up to 63 actions (with '
                       'more the actors sample with torch.multinomial).  bf16 '
                       'inference runs ops.')
-  p.add_argument('--torso_blocks', default='ops', choices=['ops', 'fused'],
+  p.add_argument('--torso_blocks', default='ops', choices=['ops', 'fused', 'stage'],
                  help='Residual blocks of the fp32 HIP deep torso in actor '
                       'inference (no autograd, at most 512 frames per launch): '
                       'ops = two Winograd convs per block; fused = ONE kernel '
-                      'per block, bitwise the same features.  bf16 inference '
-                      'fuses its blocks already; the shallow torso and the '
-                      'torch backend have nothing to fuse and run as with ops.')
+                      'per block; stage = as fused, and the last stage (its '
+                      'head, max-pool and both blocks at an 18x24 input such '
+                      'as the 72x96 frame\'s, else its two blocks where the '
+                      'whole map fits one workgroup, e.g. 84x84 and 72x128 '
+                      'frames) in ONE kernel.  All three give bitwise the same '
+                      'features.  bf16 inference fuses its blocks already; '
+                      'the shallow torso and the torch backend have nothing '
+                      'to fuse and run as with ops.')
   p.add_argument('--inference_device', default='auto',
                  help='Device of the actor-inference model: auto = the '
                       'learner device; e.g. cuda:1 or cpu.')

@@ -135,11 +135,17 @@ class InferenceModel(object):
 
   @property
   def torso_blocks(self):
-    """'fused' when this model's torso runs each residual block as one
-    kernel (Agent(torso_blocks='fused') where it applies), else 'ops'."""
+    """The form this model's torso runs: 'stage' (the last stage, or its two
+    blocks, in one kernel and every other residual block as one kernel:
+    Agent(torso_blocks='stage') where the stage kernel takes the frames),
+    'fused' (one kernel per residual block: 'fused', or 'stage' on frames the
+    stage kernel does not take), else 'ops'."""
+    cuda = self.device.type == 'cuda'
     fused = getattr(self.agent, 'torso_blocks_fused', None)
-    return ('fused' if fused is not None and
-            fused(self.device.type == 'cuda') else 'ops')
+    if fused is None or not fused(cuda):
+      return 'ops'
+    form = getattr(self.agent, 'torso_stage_form', None)
+    return 'stage' if form is not None and form(cuda) else 'fused'
 
   @torch.no_grad()
   def step_device(self, last_action, reward, done, frame, instr_ids,

@@ -128,8 +128,10 @@ class Agent(nn.Module):
     # 'fused': a no-grad forward of the fp32 HIP deep torso on a board's
     # worth of frames runs each residual block as ONE kernel
     # (ops/conv_f32.py _DeepTorsoF32Infer) where it applies
-    # (torso_blocks_fused); 'ops': two Winograd convs per block
-    if torso_blocks not in ('ops', 'fused'):
+    # (torso_blocks_fused); 'stage': the same, and the last stage in one
+    # launch where its whole map fits a workgroup (_DeepTorsoF32Stage);
+    # 'ops': two Winograd convs per block
+    if torso_blocks not in ('ops', 'fused', 'stage'):
       raise ValueError('unknown torso_blocks %r' % (torso_blocks,))
     self.torso_blocks = torso_blocks
     # 'fused': the T = 1 inference step after the torso-FC GEMM is ONE kernel
@@ -531,12 +533,23 @@ class Agent(nn.Module):
             isinstance(generator, PhiloxStream))
 
   def torso_blocks_fused(self, cuda=True):
-    """True when `torso_blocks='fused'` is honoured for a no-grad forward of
-    CUDA frames: HIP backend, deep torso, and the exact-fp32 torso kernels
-    run it (the bf16 torso fuses its blocks on its own; the shallow torso has
-    none).  Otherwise the torso runs as with 'ops'."""
-    return (self.torso_blocks == 'fused' and self.backend == 'hip' and cuda and
-            self.torso_kind == 'deep' and not _bf16_torso_ready(self))
+    """True when `torso_blocks='fused'` or `'stage'` is honoured for a no-grad
+    forward of CUDA frames: HIP backend, deep torso, and the exact-fp32 torso
+    kernels run it (the bf16 torso fuses its blocks on its own; the shallow
+    torso has none).  Otherwise the torso runs as with 'ops'."""
+    return (self.torso_blocks in ('fused', 'stage') and self.backend == 'hip'
+            and cuda and self.torso_kind == 'deep' and
+            not _bf16_torso_ready(self))
+
+  def torso_stage_form(self, cuda=True):
+    """What `torso_blocks='stage'` runs for the last stage of this agent's
+    frames: 'stage' (head, pool and both blocks in one launch), 'tail' (both
+    blocks in one launch), or None: not asked for, or the torso runs as
+    'fused' / 'ops' there (torso_blocks_fused)."""
+    if self.torso_blocks != 'stage' or not self.torso_blocks_fused(cuda):
+      return None
+    from ..ops import conv_f32
+    return conv_f32.stage_form(self.frame_shape)
 
   def _fused_step(self, actions, env_outputs, core_state, generator, epilogue):
     """The T = 1 actor step with the fused core: torso, the torso-FC GEMM

@@ -174,10 +174,33 @@ class _DeepTorsoF32Infer(_DeepTorsoF32):
     raise RuntimeError('the inference torso has no backward')
 
 
-def _deep_forward(ctx, frames, params):
+class _DeepTorsoF32Stage(_DeepTorsoF32Infer):
+  """Agent(torso_blocks='stage'): as _DeepTorsoF32Infer, and the last stage
+  is one launch where the stage kernel takes it."""
+
+  @staticmethod
+  def forward(ctx, frames, *params):
+    return _deep_forward(None, frames, params, stage=True)
+
+
+def stage_form(frame_shape, frames=1):
+  """What torso_blocks='stage' runs for the last stage of the deep torso on
+  frames of this shape: 'stage' (cf32_stage_fwd: head, pool and both blocks),
+  'tail' (cf32_stage_tail_fwd: both blocks) or None (one launch per block, as
+  'fused').  The launchers' own checks, host arithmetic only."""
+  h, w = frame_shape[0], frame_shape[1]
+  for _ in range(2):  # the 3x3/2 SAME pools of stages 0 and 1
+    h, w = (h + 1) // 2, (w + 1) // 2
+  return {2: 'stage', 1: 'tail'}.get(ext().cf32_stage_form(frames, h, w, 32))
+
+
+def _deep_forward(ctx, frames, params, stage=False):
   """Forward of the deep torso.  ctx None (_DeepTorsoF32Infer): residual
   blocks run cf32_res_block_fwd (both convs in one launch, t only in LDS,
-  bitwise the two launches) where that kernel takes the shape."""
+  bitwise the two launches) where that kernel takes the shape.  stage
+  (_DeepTorsoF32Stage): the last stage runs cf32_stage_fwd (head, pool and
+  both blocks in one launch), else its two blocks cf32_stage_tail_fwd, where
+  those take the shape; bitwise again."""
   C = ext()
   fused_blocks = ctx is None
   # stage 0 reads a 4-channel fp32 x / 255 image (one 16-B load per pixel
@@ -195,6 +218,11 @@ def _deep_forward(ctx, frames, params):
     H, W = x.shape[1], x.shape[2]
     pbh = layers.same_pads(H, 3, 2)[0]
     pbw = layers.same_pads(W, 3, 2)[0]
+    if stage and s == 2 and x.dtype == torch.float32:
+      y = C.cf32_stage_fwd(x, w, b, *params[p:p + 8], True)
+      if y:
+        x = y[0]
+        break
     fused = (C.cf32_wino_conv_pool_fwd(x, w, b) if x.dtype == torch.float32
              else [])
     if fused:
@@ -216,6 +244,11 @@ def _deep_forward(ctx, frames, params):
                        frames.shape[3] <= 4 and xa.shape[3] == 16)
             else x)
     saved += [keep, arg]
+    if stage and s == 2:
+      y = C.cf32_stage_tail_fwd(xa, *params[p:p + 8], True)
+      if y:
+        x = y[0]
+        break
     for blk in range(2):
       w1, b1, w2, b2 = params[p:p + 4]
       p += 4
@@ -362,12 +395,13 @@ def torso_forward_f32(agent, frames):
     params = [cache['w0pad']] + params[1:]
   from .conv import FUSED_BLOCK_MAX_FRAMES
   # actor inference (no autograd, a board's worth of frames) of an agent
-  # built with torso_blocks='fused': one launch per residual block
-  fn = (_DeepTorsoF32Infer
-        if (getattr(agent, 'torso_blocks', 'ops') == 'fused' and
-            not torch.is_grad_enabled() and
-            frames.shape[0] <= FUSED_BLOCK_MAX_FRAMES)
-        else _DeepTorsoF32)
+  # built with torso_blocks='fused': one launch per residual block; 'stage':
+  # and one for the last stage
+  blocks = getattr(agent, 'torso_blocks', 'ops')
+  fn = _DeepTorsoF32
+  if (blocks in ('fused', 'stage') and not torch.is_grad_enabled() and
+      frames.shape[0] <= FUSED_BLOCK_MAX_FRAMES):
+    fn = _DeepTorsoF32Stage if blocks == 'stage' else _DeepTorsoF32Infer
   return _chunked(fn, frames, params)
 
 

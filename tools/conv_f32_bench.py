@@ -143,6 +143,52 @@ if (not ONLY or ONLY in 'block') and N <= 512:
       print('%-14s N=%-4d %s block fwd: conv1 %6.1f + conv2 %6.1f = %6.1f us | fused '
             '%6.1f us (band %d rows)' % (name, N, label, t1, t2, t1 + t2, tb,
                                         C.cf32_res_block_band(Cc, W)), flush=True)
+# the whole last stage at an actor-inference batch in the three forms of
+# --torso_blocks: ops (head + 4 convs), fused (head + 2 block launches), stage
+# (one launch where cf32_stage_fwd takes the input, else head + one launch
+# for both blocks); filter 'stage'
+if (not ONLY or ONLY in 'stage') and N <= 512:
+  for name, H, W in [('18x24 -> 9x12', 18, 24), ('21x21 -> 11x11', 21, 21),
+                     ('18x32 -> 9x16', 18, 32)]:
+    h, w_ = (H + 1) // 2, (W + 1) // 2
+    x = torch.randn(N, H, W, 32, device=dev)
+    wh = torch.randn(3, 3, 32, 32, device=dev) * 0.1
+    bh = torch.randn(32, device=dev)
+    tail = []
+    for _ in range(4):
+      tail += [torch.randn(3, 3, 32, 32, device=dev) * 0.1, torch.randn(32, device=dev)]
+
+    def head():
+      out = C.cf32_wino_conv_pool_fwd(x, wh, bh)
+      if out:
+        return out[0]
+      pb = (0 if H % 2 == 0 else 1, 0 if W % 2 == 0 else 1)
+      return C.cf32_maxpool_fwd(C.cf32_conv_fwd(x, wh, bh, 1, 1, 1, H, W), *pb)[0]
+
+    def f_ops():
+      xa = head()
+      for k in range(2):
+        w1, b1, w2, b2 = tail[4 * k:4 * k + 4]
+        t = C.cf32_conv_fwd(xa, w1, b1, 1, 1, 1, h, w_, relu_in=True, relu_out=True)
+        xa = C.cf32_conv_fwd(t, w2, b2, 1, 1, 1, h, w_, add=xa, relu_out=k == 1)
+      return xa
+
+    def f_fused():
+      xa = head()
+      for k in range(2):
+        xa = C.cf32_res_block_fwd(xa, *tail[4 * k:4 * k + 4], k == 1)[0]
+      return xa
+
+    def f_stage():
+      out = C.cf32_stage_fwd(x, wh, bh, *tail, True)
+      return out[0] if out else C.cf32_stage_tail_fwd(head(), *tail, True)[0]
+
+    form = {2: 'one launch', 1: 'head + one launch', 0: 'declined'}[
+        C.cf32_stage_form(N, H, W, 32)]
+    assert form != 'declined' and torch.equal(f_stage(), f_ops()), name
+    for label, tm in (('eager', timeit), ('graph', timeit_graph)):
+      print('last stage %-15s N=%-4d %s: ops %6.1f us | fused %6.1f us | stage %6.1f us (%s)' % (
+          name, N, label, tm(f_ops), tm(f_fused), tm(f_stage), form), flush=True)
 if ONLY:
   sys.exit(0)
 xp =torch.randn(N, 72, 96, 16, device=dev)

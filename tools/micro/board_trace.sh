@@ -2,7 +2,9 @@
 # Kernel trace of an end-to-end config-#4 run with the inference board, then
 # tools/micro/board_trace.py on the learner process's database; only the
 # summary stays under gpurun_out (the database is larger than gpurun's pull
-# limit).  Extra experiment.py flags follow.  usage: board_trace.sh TAG [flags]
+# limit).  Extra experiment.py flags follow (e.g. --inference_dtype=fp32
+# --inference_lanes=2 --torso_blocks=ops|fused|stage).
+# usage: board_trace.sh TAG [flags]
 set -e
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/../..}"
 tag=$1; shift
