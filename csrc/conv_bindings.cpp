@@ -206,6 +206,18 @@ void register_conv_ops(pybind11::module& m) {
         pybind11::arg("db"), pybind11::arg("relu_act") = true);
   m.def("pool_conv_bwd", &pool_conv_bwd);
   m.def("conv1_pool_bwd", &conv1_pool_bwd);
+  // read-only record of a family's last launch ("" = the most recent one)
+  m.def("conv_launch_info", [](const std::string& family) {
+          const sa::conv::LaunchInfo i = sa::conv::launch_info(family.c_str());
+          pybind11::dict d;
+          d["family"] = std::string(i.family);
+          d["grid"] = i.grid;
+          d["grid_max"] = i.grid_max;
+          d["ntiles"] = i.ntiles;
+          d["rows"] = i.rows;
+          d["specialized"] = i.specialized;
+          return d;
+        }, pybind11::arg("family") = "");
   m.def("conv_tune", [](const std::string& key, int64_t value) {
           return sa::conv::conv_tune_set(key.c_str(), static_cast<int>(value));
         }, pybind11::arg("key"), pybind11::arg("value") = -1);

@@ -47,5 +47,19 @@ void conv1_pool_bwd_launch(const void* dP, const uint8_t* argmax,
 // per-workgroup slots in a fixed order instead of with float atomics.
 int64_t wgrad_part_floats(int cin, int cout, bool conv1);
 
+// Read-only record of the last launch of a launcher family (host side; the
+// tests assert from it that the path they mean to test actually ran).
+struct LaunchInfo {
+  const char* family;  // "res_conv_fwd", ..., "conv1_pool_bwd"; "" = none yet
+  int grid;            // workgroups launched
+  int grid_max;        // persistent grid before the min with ntiles
+  int ntiles;          // tiles the workgroups walked
+  int rows;            // tile height (pooled rows for the pool forwards)
+  bool specialized;    // a compile-time geometry was picked
+};
+// family == nullptr or "": the most recent launch of any family.  An unknown
+// family, or one not launched yet, gives a record with family "".
+LaunchInfo launch_info(const char* family);
+
 }  // namespace conv
 }  // namespace sa

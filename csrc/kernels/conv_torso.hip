@@ -1550,12 +1550,14 @@ int num_cus() {
 // Persistent grid: enough workgroups for `per_cu` resident per CU, on the
 // CUs the fp32 torso's grids use too (conv_f32.hip conv_cus: all but the
 // CUs per XCD reserved for a concurrent stream, cf32_cu_reserve).
-int grid_for(int ntiles, size_t smem, int per_cu_cap) {
+// *grid_max: the persistent grid before the min with ntiles.
+int grid_for(int ntiles, size_t smem, int per_cu_cap, int* grid_max) {
   int per_cu = static_cast<int>((160 * 1024) / (smem + 1024));
   if (per_cu > per_cu_cap) per_cu = per_cu_cap;
   if (per_cu < 1) per_cu = 1;
   const int reserved = num_cus() - sa::cf32::conv_cus();  // 8 R on MI355X
   const int g = (num_cus() - reserved) * per_cu;
+  *grid_max = g;
   return ntiles < g ? ntiles : g;
 }
 
@@ -1726,28 +1728,44 @@ bool geo_try(int H, int W, int R, F& f) {
 enum Stage { kConv1, kStage1, kStage2, kStage3 };
 
 // R(H, W) for a kernel family, as a constexpr functor.
+// Returns whether a compiled geometry matched.
 template <int STAGE, typename RF, typename F>
-void with_geo(int H, int W, int R, F&& f) {
+bool with_geo(int H, int W, int R, F&& f) {
   if (g_tune.specialize) {
     if constexpr (STAGE == kConv1) {
-      if (geo_try<72, 96, RF::rows(72, 96)>(H, W, R, f)) return;
-      if (geo_try<72, 128, RF::rows(72, 128)>(H, W, R, f)) return;
-      if (geo_try<84, 84, RF::rows(84, 84)>(H, W, R, f)) return;
+      if (geo_try<72, 96, RF::rows(72, 96)>(H, W, R, f)) return true;
+      if (geo_try<72, 128, RF::rows(72, 128)>(H, W, R, f)) return true;
+      if (geo_try<84, 84, RF::rows(84, 84)>(H, W, R, f)) return true;
     } else if constexpr (STAGE == kStage1) {
-      if (geo_try<36, 48, RF::rows(36, 48)>(H, W, R, f)) return;
-      if (geo_try<36, 64, RF::rows(36, 64)>(H, W, R, f)) return;
-      if (geo_try<42, 42, RF::rows(42, 42)>(H, W, R, f)) return;
+      if (geo_try<36, 48, RF::rows(36, 48)>(H, W, R, f)) return true;
+      if (geo_try<36, 64, RF::rows(36, 64)>(H, W, R, f)) return true;
+      if (geo_try<42, 42, RF::rows(42, 42)>(H, W, R, f)) return true;
     } else if constexpr (STAGE == kStage2) {
-      if (geo_try<18, 24, RF::rows(18, 24)>(H, W, R, f)) return;
-      if (geo_try<18, 32, RF::rows(18, 32)>(H, W, R, f)) return;
-      if (geo_try<21, 21, RF::rows(21, 21)>(H, W, R, f)) return;
+      if (geo_try<18, 24, RF::rows(18, 24)>(H, W, R, f)) return true;
+      if (geo_try<18, 32, RF::rows(18, 32)>(H, W, R, f)) return true;
+      if (geo_try<21, 21, RF::rows(21, 21)>(H, W, R, f)) return true;
     } else {
-      if (geo_try<9, 12, RF::rows(9, 12)>(H, W, R, f)) return;
-      if (geo_try<9, 16, RF::rows(9, 16)>(H, W, R, f)) return;
-      if (geo_try<11, 11, RF::rows(11, 11)>(H, W, R, f)) return;
+      if (geo_try<9, 12, RF::rows(9, 12)>(H, W, R, f)) return true;
+      if (geo_try<9, 16, RF::rows(9, 16)>(H, W, R, f)) return true;
+      if (geo_try<11, 11, RF::rows(11, 11)>(H, W, R, f)) return true;
     }
   }
   f(IC<0>{}, IC<0>{}, IC<0>{});
+  return false;
+}
+
+// Launch records, one per launcher family (launch_info()).
+enum Family { kResConvFwd, kResBlockFwd, kConvPoolFwd, kConv1PoolFwd,
+              kResConvBwd, kPoolConvBwd, kConv1PoolBwd, kFamilies };
+constexpr const char* kFamilyName[kFamilies] = {
+    "res_conv_fwd", "res_block_fwd", "conv_pool_fwd", "conv1_pool_fwd",
+    "res_conv_bwd", "pool_conv_bwd", "conv1_pool_bwd"};
+LaunchInfo g_launch[kFamilies] = {};
+int g_last_family = -1;
+void note_launch(Family f, int grid, int grid_max, int ntiles, int rows,
+                 bool specialized) {
+  g_launch[f] = LaunchInfo{kFamilyName[f], grid, grid_max, ntiles, rows, specialized};
+  g_last_family = f;
 }
 
 template <int C>
@@ -1781,6 +1799,14 @@ struct RowsConv1Bwd {
 
 }  // namespace
 
+LaunchInfo launch_info(const char* family) {
+  if (!family || !*family)
+    return g_last_family < 0 ? LaunchInfo{"", 0, 0, 0, 0, false} : g_launch[g_last_family];
+  for (int f = 0; f < kFamilies; ++f)
+    if (std::strcmp(kFamilyName[f], family) == 0 && g_launch[f].family) return g_launch[f];
+  return LaunchInfo{"", 0, 0, 0, 0, false};
+}
+
 int res_conv_rows(int H, int W) { return rows_for(H, W, 32, g_tune.px_res_fwd); }
 
 void res_block_fwd_launch(const void* x, const float* w1, const float* b1,
@@ -1794,7 +1820,8 @@ void res_block_fwd_launch(const void* x, const float* w1, const float* b1,
   const int ntiles = N * ((H + R - 1) / R);
   const size_t smem = (2 * w_lds_elems(C, C, true) + (R + 4) * row_pitch(C, W) + C +
                        (R + 2) * row_pitch(C, W) + C) * sizeof(bf16_t);
-  const int grid = grid_for(ntiles, smem, g_tune.cap_fwd);
+  int grid_max = 0;
+  const int grid = grid_for(ntiles, smem, g_tune.cap_fwd, &grid_max);
   auto X = static_cast<const bf16_t*>(x);
   auto Tt = static_cast<bf16_t*>(t);
   auto Y = static_cast<bf16_t*>(y);
@@ -1804,8 +1831,10 @@ void res_block_fwd_launch(const void* x, const float* w1, const float* b1,
     hipLaunchKernelGGL(kernel, dim3(grid), dim3(kThreads), smem, s, X, w1, b1,
                        w2, b2, Tt, Y, N, H, W, R, xcd);
   };
+  bool spec = false;
 #define SA_RB(CC, PR, STG)                                                     \
-  with_geo<STG, RowsBlockFwd<CC>>(H, W, R, [&](auto h, auto ww, auto r) {      \
+  spec = with_geo<STG, RowsBlockFwd<CC>>(H, W, R,                              \
+                  [&](auto h, auto ww, auto r) {                               \
     go(res_block_fwd_kernel<CC, PR, decltype(h)::value, decltype(ww)::value,   \
                             decltype(r)::value>);                              \
   })
@@ -1817,6 +1846,7 @@ void res_block_fwd_launch(const void* x, const float* w1, const float* b1,
     if (post_relu) SA_RB(32, true, kStage3); else SA_RB(32, false, kStage3);
   }
 #undef SA_RB
+  note_launch(kResBlockFwd, grid, grid_max, ntiles, R, spec);
 }
 
 void res_conv_fwd_launch(const void* x, const float* w, const float* b,
@@ -1828,7 +1858,8 @@ void res_conv_fwd_launch(const void* x, const float* w, const float* b,
               "res_conv_fwd");
   const int ntiles = N * ((H + R - 1) / R);
   const size_t smem = (w_lds_elems(C, C, true) + (R + 2) * row_pitch(C, W) + C) * sizeof(bf16_t);
-  const int grid = grid_for(ntiles, smem, g_tune.cap_fwd);
+  int grid_max = 0;
+  const int grid = grid_for(ntiles, smem, g_tune.cap_fwd, &grid_max);
   auto X = static_cast<const bf16_t*>(x);
   auto RS = static_cast<const bf16_t*>(resid);
   auto Y = static_cast<bf16_t*>(y);
@@ -1838,8 +1869,10 @@ void res_conv_fwd_launch(const void* x, const float* w, const float* b,
     hipLaunchKernelGGL(kernel, dim3(grid), dim3(kThreads), smem, s, X, w, b,
                        RS, Y, N, H, W, R, xcd);
   };
+  bool spec = false;
 #define SA_RF(CC, RE, PR, RI, STG)                                             \
-  with_geo<STG, RowsResFwd<CC>>(H, W, R, [&](auto h, auto ww, auto r) {        \
+  spec = with_geo<STG, RowsResFwd<CC>>(H, W, R,                                \
+                  [&](auto h, auto ww, auto r) {                               \
     go(res_conv_fwd_kernel<CC, RE, PR, RI, decltype(h)::value,                 \
                            decltype(ww)::value, decltype(r)::value>);          \
   })
@@ -1864,6 +1897,7 @@ void res_conv_fwd_launch(const void* x, const float* w, const float* b,
   }
 #undef SA_RF_C
 #undef SA_RF
+  note_launch(kResConvFwd, grid, grid_max, ntiles, R, spec);
 }
 
 void conv_pool_fwd_launch(const void* x, const float* w, const float* b,
@@ -1877,7 +1911,8 @@ void conv_pool_fwd_launch(const void* x, const float* w, const float* b,
   const int ntiles = N * ((Hp + Rp - 1) / Rp);
   const size_t smem = (w_lds_elems(CIN, COUT, true) + (2 * Rp + 3) * row_pitch(CIN, W) + CIN +
                        (2 * Rp + 1) * (W + 2) * COUT) * sizeof(bf16_t);
-  const int grid = grid_for(ntiles, smem, g_tune.cap_fwd);
+  int grid_max = 0;
+  const int grid = grid_for(ntiles, smem, g_tune.cap_fwd, &grid_max);
   auto X = static_cast<const bf16_t*>(x);
   auto P = static_cast<bf16_t*>(pooled);
   const int xcd = g_tune.xcd | (g_tune.ablate << 8);
@@ -1886,8 +1921,10 @@ void conv_pool_fwd_launch(const void* x, const float* w, const float* b,
     hipLaunchKernelGGL(kernel, dim3(grid), dim3(kThreads), smem, s, X, w, b,
                        P, argmax, N, H, W, Rp, pb_h, pb_w, xcd);
   };
+  bool spec = false;
 #define SA_CP(CI, CO, STG)                                                     \
-  with_geo<STG, RowsPoolFwd<CI>>(H, W, Rp, [&](auto h, auto ww, auto r) {      \
+  spec = with_geo<STG, RowsPoolFwd<CI>>(H, W, Rp,                              \
+                  [&](auto h, auto ww, auto r) {                               \
     go(conv_pool_fwd_kernel<CI, CO, decltype(h)::value, decltype(ww)::value,   \
                             decltype(r)::value>);                              \
   })
@@ -1895,6 +1932,7 @@ void conv_pool_fwd_launch(const void* x, const float* w, const float* b,
   else if (CIN == 32 && COUT == 32) SA_CP(32, 32, kStage2);
   else if (CIN == 16 && COUT == 16) SA_CP(16, 16, kStage1);
 #undef SA_CP
+  note_launch(kConvPoolFwd, grid, grid_max, ntiles, Rp, spec);
 }
 
 void conv1_pool_fwd_launch(const uint8_t* x, const float* w, const float* b,
@@ -1906,11 +1944,13 @@ void conv1_pool_fwd_launch(const uint8_t* x, const float* w, const float* b,
   const int ntiles = N * ((Hp + Rp - 1) / Rp);
   const size_t smem = (3 * 16 * 16 + (2 * Rp + 1) * (W + 2) * 16 +
                        ((2 * Rp + 3) * (W + 2) + 4) * 4) * sizeof(bf16_t);
-  const int grid = grid_for(ntiles, smem, g_tune.cap_fwd);
+  int grid_max = 0;
+  const int grid = grid_for(ntiles, smem, g_tune.cap_fwd, &grid_max);
   auto P = static_cast<bf16_t*>(pooled);
   const int xcd = g_tune.xcd | (g_tune.ablate << 8);
   require_fit(C == 3 || C == 4, "conv1_pool_fwd: 3 or 4 frame channels");
-  with_geo<kConv1, RowsConv1Fwd>(H, W, Rp, [&](auto h, auto ww, auto r) {
+  const bool spec = with_geo<kConv1, RowsConv1Fwd>(H, W, Rp, [&](auto h, auto ww,
+                                                                 auto r) {
     auto k3 = conv1_pool_fwd_kernel<3, decltype(h)::value, decltype(ww)::value,
                                     decltype(r)::value>;
     auto k4 = conv1_pool_fwd_kernel<4, decltype(h)::value, decltype(ww)::value,
@@ -1920,6 +1960,7 @@ void conv1_pool_fwd_launch(const uint8_t* x, const float* w, const float* b,
     hipLaunchKernelGGL(k, dim3(grid), dim3(kThreads), smem, s, x, w, b, P,
                        argmax, N, H, W, Rp, pb_h, pb_w, xcd);
   });
+  note_launch(kConv1PoolFwd, grid, grid_max, ntiles, Rp, spec);
 }
 
 // Deterministic mode: floats of the slot workspace a wgrad launch needs (0
@@ -1948,7 +1989,8 @@ void res_conv_bwd_launch(const void* dy, const void* act, const void* skip,
               "res_conv_bwd");
   const int ntiles = N * ((H + R - 1) / R);
   const size_t smem = (w_lds_elems(C, C, false) + 2 * ((R + 2) * row_pitch(C, W) + C)) * sizeof(bf16_t);
-  const int grid = grid_for(ntiles, smem, g_tune.cap_bwd);
+  int grid_max = 0;
+  const int grid = grid_for(ntiles, smem, g_tune.cap_bwd, &grid_max);
   auto DY = static_cast<const bf16_t*>(dy);
   auto A = static_cast<const bf16_t*>(act);
   auto SK = static_cast<const bf16_t*>(skip);
@@ -1959,8 +2001,10 @@ void res_conv_bwd_launch(const void* dy, const void* act, const void* skip,
     hipLaunchKernelGGL(kernel, dim3(grid), dim3(kThreads), smem, s, DY, A, SK,
                        w, DX, dw, db, N, H, W, R, xcd, part);
   };
+  bool spec = false;
 #define SA_RB(CC, SKP, RA, STG)                                                \
-  with_geo<STG, RowsResBwd<CC>>(H, W, R, [&](auto h, auto ww, auto r) {        \
+  spec = with_geo<STG, RowsResBwd<CC>>(H, W, R,                                \
+                  [&](auto h, auto ww, auto r) {                               \
     go(res_conv_bwd_kernel<CC, SKP, RA, decltype(h)::value,                    \
                            decltype(ww)::value, decltype(r)::value>);          \
   })
@@ -1978,6 +2022,7 @@ void res_conv_bwd_launch(const void* dy, const void* act, const void* skip,
   }
 #undef SA_RB_C
 #undef SA_RB
+  note_launch(kResConvBwd, grid, grid_max, ntiles, R, spec);
   if (part) reduce_slots(part, grid, 9 * C * C + C, 9 * C * C, dw, db, s);
 }
 
@@ -1997,7 +2042,8 @@ void pool_conv_bwd_launch(const void* dP, const uint8_t* argmax, const void* x,
                        (R + 2) * (row_pitch(CIN, W) + row_pitch(COUT, W)) +
                        CIN + COUT + prow_max * Wo * COUT) * sizeof(bf16_t) +
                       prow_max * Wo * COUT;
-  const int grid = grid_for(ntiles, smem, g_tune.cap_bwd);
+  int grid_max = 0;
+  const int grid = grid_for(ntiles, smem, g_tune.cap_bwd, &grid_max);
   auto DP = static_cast<const bf16_t*>(dP);
   auto X = static_cast<const bf16_t*>(x);
   auto DX = static_cast<bf16_t*>(dx);
@@ -2007,8 +2053,10 @@ void pool_conv_bwd_launch(const void* dP, const uint8_t* argmax, const void* x,
     hipLaunchKernelGGL(kernel, dim3(grid), dim3(kThreads), smem, s, DP, argmax,
                        X, w, DX, dw, db, N, H, W, R, pb_h, pb_w, xcd, part);
   };
+  bool spec = false;
 #define SA_PB(CI, CO, NDX, STG)                                                \
-  with_geo<STG, RowsPoolBwd<CI, CO>>(H, W, R, [&](auto h, auto ww, auto r) {   \
+  spec = with_geo<STG, RowsPoolBwd<CI, CO>>(H, W, R,                           \
+                  [&](auto h, auto ww, auto r) {                               \
     go(pool_conv_bwd_kernel<CI, CO, NDX, decltype(h)::value,                   \
                             decltype(ww)::value, decltype(r)::value>);         \
   })
@@ -2024,6 +2072,7 @@ void pool_conv_bwd_launch(const void* dP, const uint8_t* argmax, const void* x,
     else SA_PB(16, 16, false, kStage1);
   }
 #undef SA_PB
+  note_launch(kPoolConvBwd, grid, grid_max, ntiles, R, spec);
   if (part)
     reduce_slots(part, grid, 9 * CIN * COUT + COUT, 9 * CIN * COUT, dw, db, s);
 }
@@ -2042,11 +2091,13 @@ void conv1_pool_bwd_launch(const void* dP, const uint8_t* argmax,
   const size_t smem = ((R + 2) * (W + 2) * 16 + 16 + (((R + 2) * (W + 2) + 5) & ~1) * 4 +
                        prow_max * Wo * 16) * sizeof(bf16_t) +
                       prow_max * Wo * 16;
-  const int grid = grid_for(ntiles, smem, g_tune.cap_bwd);
+  int grid_max = 0;
+  const int grid = grid_for(ntiles, smem, g_tune.cap_bwd, &grid_max);
   auto DP = static_cast<const bf16_t*>(dP);
   const int xcd = g_tune.xcd | (g_tune.ablate << 8);
   require_fit(C == 3 || C == 4, "conv1_pool_bwd: 3 or 4 frame channels");
-  with_geo<kConv1, RowsConv1Bwd>(H, W, R, [&](auto h, auto ww, auto r) {
+  const bool spec = with_geo<kConv1, RowsConv1Bwd>(H, W, R, [&](auto h, auto ww,
+                                                                auto r) {
     auto k3 = conv1_pool_bwd_kernel<3, decltype(h)::value, decltype(ww)::value,
                                     decltype(r)::value>;
     auto k4 = conv1_pool_bwd_kernel<4, decltype(h)::value, decltype(ww)::value,
@@ -2056,6 +2107,7 @@ void conv1_pool_bwd_launch(const void* dP, const uint8_t* argmax,
     hipLaunchKernelGGL(k, dim3(grid), dim3(kThreads), smem, s, DP, argmax, x,
                        dw, db, N, H, W, R, pb_h, pb_w, xcd, part);
   });
+  note_launch(kConv1PoolBwd, grid, grid_max, ntiles, R, spec);
   if (part)
     reduce_slots(part, grid * kWaves, 9 * C * 16 + 16, 9 * C * 16, dw, db, s);
 }

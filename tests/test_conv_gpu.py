@@ -38,6 +38,9 @@ def scatter_pool_grad(dP, arg, H, W, pb_h, pb_w):
   j = torch.arange(Wo, device=dev).view(1, 1, Wo, 1)
   r = 2 * i - pb_h + a // 3
   c = 2 * j - pb_w + a % 3
+  # index_put_ wraps negative indices: a code above / left of the image must
+  # fail here, not be scattered to the far edge
+  assert bool(((r >= 0) & (r < H) & (c >= 0) & (c < W)).all())
   n = torch.arange(N, device=dev).view(N, 1, 1, 1).expand_as(a)
   ch = torch.arange(C, device=dev).view(1, 1, 1, C).expand_as(a)
   dY = torch.zeros(N, H, W, C, device=dev)
@@ -96,8 +99,10 @@ def test_conv_pool_fwd(cuda, CIN, COUT, H, W):
   a = arg.long()
   i = torch.arange(Hp, device=cuda).view(1, Hp, 1, 1)
   j = torch.arange(Wo, device=cuda).view(1, 1, Wo, 1)
-  rr = (2 * i - pb_h + a // 3).clamp(0, H - 1)
-  cc = (2 * j - pb_w + a % 3).clamp(0, W - 1)
+  rr = 2 * i - pb_h + a // 3
+  cc = 2 * j - pb_w + a % 3
+  # no clamping: a code that points into the padding is an error
+  assert bool(((rr >= 0) & (rr < H) & (cc >= 0) & (cc < W)).all())
   n = torch.arange(N, device=cuda).view(N, 1, 1, 1).expand_as(a)
   ch = torch.arange(COUT, device=cuda).view(1, 1, 1, COUT).expand_as(a)
   picked = y[n, rr, cc, ch]
