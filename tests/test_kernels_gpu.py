@@ -138,7 +138,9 @@ def recurrence(request):
 
 def _lstm_close(a, b, rtol, atol, bf16):
   """fp32 tolerances for the per-step kernels; bf16-operand accuracy (relative
-  Frobenius error < 1e-2 and loose elementwise bounds) for the gang kernels."""
+  Frobenius error < 1e-2 and loose elementwise bounds) for the gang kernels.
+  These free-running comparisons are the coarse check; the tight one, every
+  step against float64 with derived bounds, is tests/test_lstm_oracle_gpu.py."""
   if not bf16:
     torch.testing.assert_close(a, b, rtol=rtol, atol=atol)
     return
