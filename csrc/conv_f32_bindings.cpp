@@ -400,6 +400,40 @@ std::vector<at::Tensor> wino_conv_pool_fwd(at::Tensor x, at::Tensor w, at::Tenso
   return {y, arg};
 }
 
+// Stage-0 / stage-1 head for actor inference in one launch (conv_wino.hip
+// wino_head_infer_kernel): x uint8 NHWC frames with 1..4 channels (w HWIO
+// [3,3,C,16] or zero-padded to [3,3,4,16]) or float32 NHWC with 16 channels
+// (w [3,3,16,32]) -> {pooled}, bitwise cf32_frames_f32 +
+// cf32_wino_conv_pool_fwd; {} when the shape is not covered (nothing ran; the
+// caller takes those kernels)
+std::vector<at::Tensor> head_fwd(at::Tensor x, at::Tensor w, at::Tensor b) {
+  check_nhwc(x, "x");
+  check_w(w);
+  const bool u8 = src_kind(x) == sa::cf32::kSrcU8;
+  TORCH_CHECK(b.is_cuda() && b.scalar_type() == at::kFloat && b.is_contiguous() &&
+                  b.numel() == w.size(3), "bias");
+  const int64_t Cin = x.size(3), Cout = w.size(3), wcin = w.size(2);
+  if (w.size(0) != 3 || !(u8 ? (Cin >= 1 && Cin <= 4 && (wcin == Cin || wcin == 4) && Cout == 16)
+                             : (Cin == 16 && wcin == 16 && Cout == 32)))
+    return {};
+  const int64_t N = x.size(0), H = x.size(1), W = x.size(2);
+  if (H % 2 != 0 || W % 2 != 0 || N > sa::cf32::kResBlockMaxFrames || H > INT_MAX || W > INT_MAX)
+    return {};
+  if (!sa::cf32::wino_head_form(static_cast<int>(N), static_cast<int>(H), static_cast<int>(W),
+                                static_cast<int>(Cin), static_cast<int>(Cout), u8))
+    return {};
+  const c10::DeviceGuard g(x.device());
+  auto y = at::empty({N, H / 2, W / 2, Cout}, x.options().dtype(at::kFloat));
+  if (!sa::cf32::wino_head_infer_launch(x.data_ptr(), u8, w.data_ptr<float>(),
+                                        static_cast<int>(wcin), b.data_ptr<float>(),
+                                        y.data_ptr<float>(), static_cast<int>(N),
+                                        static_cast<int>(H), static_cast<int>(W),
+                                        static_cast<int>(Cin), static_cast<int>(Cout), stream()))
+    return {};
+  check_launch("cf32_head_fwd");
+  return {y};
+}
+
 // Whole residual block (actor inference): y = conv2(relu(conv1(relu(x)) + b1))
 // + b2 + x [relu when last] in one launch (conv_wino.hip
 // wino_res_block_kernel), bitwise the two cf32_conv_fwd calls; {} when the
@@ -586,6 +620,16 @@ void register_conv_f32_ops(pybind11::module& m) {
   // (cf32_stage_tail_fwd), 0 neither
   m.def("cf32_stage_form",
         [](int N, int H, int W, int C) { return sa::cf32::wino_stage_form(N, H, W, C); });
+  m.def("cf32_head_fwd", &head_fwd, arg("x"), arg("w"), arg("b"));
+  // 1 where cf32_head_fwd takes N x [H, W, cin] -> cout (uint8 frames or
+  // float32), else 0: host arithmetic only
+  m.def("cf32_head_form", [](int N, int H, int W, int cin, int cout, bool is_u8) {
+    return sa::cf32::wino_head_form(N, H, W, cin, cout, is_u8);
+  });
+  // pooled rows per workgroup of cf32_head_fwd (0: no instance); tests cross
+  // every band seam with it
+  m.def("cf32_head_band",
+        [](int H, int W, int cin) { return sa::cf32::wino_head_band(H, W, cin); });
   // output rows per workgroup of cf32_res_block_fwd for a C-channel map of
   // width W (0: no instance); tests cross every band seam with it
   m.def("cf32_res_block_band", [](int C, int W) { return sa::cf32::wino_res_block_band(C, W); });

@@ -157,6 +157,27 @@ bool wino_stage_launch(const float* x, const float* wh, const float* bh,
 // whole stage, 1 the tail (after the head's own launches), 0 neither.  Host
 // arithmetic only.
 int wino_stage_form(int N, int H, int W, int C);
+// The stage-0 / stage-1 heads of the deep torso for actor inference in one
+// launch each (conv_wino.hip wino_head_infer_kernel): conv3x3/1 SAME + bias +
+// 3x3/2 SAME max-pool, pooled [N,H/2,W/2,Cout] only (no argmax, no scratch).
+//   is_u8   x uint8 [N,H,W,Cs], Cs 1..4, Cout 16, W in {96, 84, 128},
+//           H % 4 == 0, W * Cs % 4 == 0; w HWIO [3,3,wcin,16] with wcin == Cs
+//           or zero-padded to 4; bitwise frames_f32_launch followed by
+//           wino_conv_pool_launch on the 4-channel image
+//   else    x float [N,H,W,16], Cout 32, W in {48, 42, 64}, H even; bitwise
+//           wino_conv_pool_launch (or wino_conv_launch + maxpool_fwd_launch)
+// False (nothing launched) for any other shape, above kResBlockMaxFrames
+// images, or where the launches replaced would not run in Winograd form: the
+// caller then runs those.
+bool wino_head_infer_launch(const void* x, bool is_u8, const float* w, int wcin, const float* b,
+                            float* pooled, int N, int H, int W, int Cs, int Cout,
+                            hipStream_t s);
+// 1 where wino_head_infer_launch takes N x [H, W, cin] -> cout, else 0.  Host
+// arithmetic only.
+int wino_head_form(int N, int H, int W, int cin, int cout, bool is_u8);
+// pooled rows per workgroup of that kernel (0: no instance); tests cross
+// every band seam with it
+int wino_head_band(int H, int W, int cin);
 // Stage head with the 3x3/2 SAME max-pool fused (conv_wino.hip): x [N,H,W,Cin]
 // -> pooled [N,H/2,W/2,Cout] + argmax codes, the 3x3/1 conv + bias in
 // Winograd form, the pre-pool map only in LDS.  (Cin, Cout) = (16, 32) with

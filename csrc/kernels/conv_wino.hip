@@ -3381,6 +3381,269 @@ bool run_stage_tail(const StageArgs& a, hipStream_t s) {
   return true;
 }
 
+// ------------------------------------------------- inference stage heads
+// The stage-0 and stage-1 heads of the deep torso for actor inference:
+//   pooled = maxpool3x3/2 SAME (conv3x3/1 SAME (x) + b)
+// in ONE launch that writes only the pooled map: no argmax, no side buffers,
+// no fix-up launch, and for stage 0 no fp32 x / 255 image (the uint8 rows are
+// staged as dwords and expanded through the 256-entry correctly rounded
+// x / 255 table of frames_f32_tile_kernel, so the staged values are bitwise
+// that image's; channels past Cs and weight rows past wcin are zero).
+//
+// A workgroup owns a band of BP pooled rows p0 .. p0 + BP - 1 of one image
+// (grid N x bands).  Pooled row p reads pixel rows 2p .. 2p + 2 (pad-before 0
+// for even H), so the band computes tile rows p0 .. p0 + BP of the 2x2 tile
+// grid the other Winograd kernels use: its own BP and one more for the single
+// pixel row below its last pair, recomputed as wino_res_block_kernel
+// recomputes its halo ((BP + 1) / BP of the conv's work).  Tile rows at or
+// past H / 2 are not computed and the pool skips their taps, as it skips
+// column W (padding loses).  It stages input pixel rows 2 p0 - 1 ..
+// 2 p0 + 2 BP + 2 (zeros outside the image), writes Y + b of its tile rows
+// into a pre-pool LDS image and pools from it.  Workgroups are independent:
+// the only synchronisation is __syncthreads, every loop has a fixed bound.
+//
+// Per pre-pool element the arithmetic is wino_conv_pool_kernel's: the same
+// weight / input / output transforms (wino_core.h), for CIN == 4 its channel
+// planes (odd plane stride) and one scalar-transformed channel per lane
+// group, for CIN == 16 wino_conv_kernel's [pixel][CIN + 4] rows through
+// wino_tile; max is exact, so the pooled map is bitwise that of
+// frames_f32 + wino_conv_pool_fwd (tests/test_head_infer_f32_gpu.py).  The
+// pool phase takes the conflict-free PoolLaneMap of pitches 20 and 36.
+//
+// Instances (8 pooled rows never fit: the pre-pool image dominates), LDS bytes
+// = U + staged rows + pre-pool image (+ the table), one workgroup per CU each:
+//   stage 0   W  96  BP 6  8 waves  4096 +  25104 + 107520 + 1024 = 137744
+//             W  84  BP 6  8 waves  4096 +  22032 +  94080 + 1024 = 121232
+//             W 128  BP 4  8 waves  4096 +  24976 + 102400 + 1024 = 132496
+//   stage 1   W  48  BP 3 12 waves 32768 +  40000 +  55296        = 128064
+//             W  42  BP 3 12 waves 32768 +  35200 +  48384        = 116352
+//             W  64  BP 3  8 waves 32768 +  52800 +  73728        = 159296
+// Workgroups at 76 frames: 456 / 532 / 684 (stage 0: 72x96, 84x84, 72x128)
+// and 456 / 532 / 456 (stage 1), 1.8 - 2.7 per CU; the 76-frame launch
+// therefore runs two to three rounds of one workgroup per CU.  VGPRs 93
+// (stage 0), 120 (stage 1, 12 waves), 130 (36x64), no spills, no scratch;
+// timings: profiles/experiments.md, "One-launch inference stage heads".
+struct HeadArgs {
+  const void* x;      // uint8 [N, H, W, Cs] (CIN 4) or float [N, H, W, 16]
+  const float* w;     // HWIO [3, 3, wcin, COUT]
+  const float* bias;  // [COUT]
+  float* pooled;      // [N, H/2, W/2, COUT]
+  int N, H, Cs, wcin, nbands;
+};
+
+template <int CIN, int COUT, int W, int BP>
+struct HeadGeo {
+  static constexpr int TX = W / 2, WP = W / 2, CQ = COUT / 4, Wl = W + 2;
+  static constexpr int ROWS = 2 * BP + 4;             // staged pixel rows
+  static constexpr int IROWS = 2 * BP + 2;            // pre-pool rows (BP + 1 tile rows)
+  static constexpr int PP = CIN == 4 ? 4 : CIN + 4;   // staged pixel pitch (floats)
+  static constexpr int IPP = COUT + 4;                // pre-pool image pixel pitch
+  static constexpr int PS = (ROWS * Wl) | 1;          // CIN 4: channel-plane stride
+  static constexpr int XS = ((CIN == 4 ? 4 * PS : ROWS * Wl * PP) + 3) & ~3;
+  static constexpr int IMG = IROWS * W * IPP;
+  static constexpr int LUT = CIN == 4 ? 256 : 0;
+  static constexpr size_t bytes = sizeof(float) * (16 * CIN * COUT + XS + IMG + LUT);
+};
+
+template <int CIN, int COUT, int W, int BP, int NW>
+__global__ __launch_bounds__(64 * NW) void wino_head_infer_kernel(HeadArgs a) {
+  using P = HeadGeo<CIN, COUT, W, BP>;
+  constexpr int NTH = 64 * NW, TX = P::TX, WP = P::WP, CQ = P::CQ, Wl = P::Wl;
+  constexpr int ROWS = P::ROWS, PP = P::PP, IPP = P::IPP, PS = P::PS, NS = COUT / 16;
+  static_assert((CIN == 4 && COUT == 16) || (CIN == 16 && COUT == 32), "stage 0 or 1");
+  static_assert(W % 2 == 0 && NTH >= 256 && P::bytes <= 160 * 1024, "shape");
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  // U: CIN 16 [16 xi][4 g][COUT][4 v] (f4 A fragments), CIN 4 [16 xi][4 ci][COUT]
+  float* U_s = smem;
+  float* x_s = smem + 16 * CIN * COUT;  // CIN 4: planes [4][ROWS][Wl]; 16: [ROWS][Wl][PP]
+  float* img = x_s + P::XS;             // [IROWS][W][IPP]: pixel row 2 p0 + L
+
+  const int n = blockIdx.x / a.nbands, band = blockIdx.x - n * a.nbands;
+  const int p0 = band * BP;
+  const int H = a.H, Hp = H / 2;  // Hp: pooled rows = tile rows
+
+  if constexpr (CIN == 16) {
+    wino_u_to_lds<1, COUT, NTH>(U_s, CIN * COUT, [&](int ky, int kx, int ci, int co) {
+      return a.w[((ky * 3 + kx) * CIN + ci) * COUT + co];
+    });
+    // the raw rows (a buffer load past the end returns zeros: the padding
+    // needs no select), as wino_res_block_kernel stages them
+    constexpr int C4 = CIN / 4, KB = 4, nx = ROWS * Wl * C4;
+    const auto srcr = buf_rsrc(static_cast<const float*>(a.x),
+                               static_cast<int64_t>(a.N) * H * W * CIN);
+    for (int e0 = threadIdx.x; e0 < nx; e0 += KB * NTH) {
+      f4 stg[KB];
+#pragma unroll
+      for (int k = 0; k < KB; ++k) {
+        const int e = e0 + k * NTH;
+        const int ch = e & (C4 - 1), pix = e >> 2;
+        const int L = pix / Wl, col = pix - L * Wl;
+        const int y = 2 * p0 - 1 + L, xc = col - 1;
+        const bool in = e < nx && y >= 0 && y < H && xc >= 0 && xc < W;
+        stg[k] = bload(srcr, in ? static_cast<uint32_t>(((n * H + y) * W + xc) * CIN + 4 * ch) * 4u
+                                : kOOB);
+      }
+#pragma unroll
+      for (int k = 0; k < KB; ++k) {
+        const int e = e0 + k * NTH;
+        if (e < nx) *reinterpret_cast<f4*>(x_s + (e >> 2) * PP + 4 * (e & (C4 - 1))) = stg[k];
+      }
+    }
+  } else {
+    for (int e = threadIdx.x; e < CIN * COUT; e += NTH) {
+      const int co = e % COUT, ci = e / COUT;
+      float gk[3][3];
+#pragma unroll
+      for (int ky = 0; ky < 3; ++ky)
+#pragma unroll
+        for (int kx = 0; kx < 3; ++kx)
+          gk[ky][kx] = ci < a.wcin ? a.w[((ky * 3 + kx) * a.wcin + ci) * COUT + co] : 0.f;
+      float u[16];
+      wino_weight_transform(gk, u);
+#pragma unroll
+      for (int xi = 0; xi < 16; ++xi) U_s[(xi * 4 + ci) * COUT + co] = u[xi];
+    }
+    // the x / 255 table (the correctly rounded quotients, as
+    // frames_f32_tile_kernel), zero planes (padding, channels past Cs), then
+    // the band's uint8 rows as dwords: byte i of a row is channel i % Cs of
+    // pixel i / Cs; a row outside the image reads zeros (lut[0] = 0)
+    float* lut = img + P::IMG;
+    if (threadIdx.x < 256)
+      lut[threadIdx.x] = static_cast<float>(static_cast<double>(threadIdx.x) / 255.0);
+    for (int e = threadIdx.x; e < P::XS; e += NTH) x_s[e] = 0.f;
+    __syncthreads();
+    const int Cs = a.Cs, RD = W * Cs / 4, nd = ROWS * RD;
+    const auto srcr = __builtin_amdgcn_make_buffer_rsrc(
+        const_cast<void*>(a.x), 0,
+        static_cast<int>(static_cast<uint32_t>(static_cast<int64_t>(a.N) * H * W * Cs)),
+        0x00020000);
+    constexpr int KB = 4;
+    for (int e0 = threadIdx.x; e0 < nd; e0 += KB * NTH) {
+      uint32_t stg[KB];
+#pragma unroll
+      for (int k = 0; k < KB; ++k) {
+        const int e = e0 + k * NTH;
+        const int L = e / RD, d = e - L * RD;
+        const int y = 2 * p0 - 1 + L;
+        const bool in = e < nd && y >= 0 && y < H;
+        stg[k] = __builtin_amdgcn_raw_buffer_load_b32(
+            srcr, in ? static_cast<uint32_t>((n * H + y) * RD + d) * 4u : kOOB, 0, 0);
+      }
+#pragma unroll
+      for (int k = 0; k < KB; ++k) {
+        const int e = e0 + k * NTH;
+        if (e >= nd) continue;
+        const int L = e / RD, d = e - L * RD;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          const int i = 4 * d + q;
+          const int pix = Cs == 4 ? d : (Cs == 3 ? i / 3 : (Cs == 2 ? i >> 1 : i));
+          const int ch = i - pix * Cs;
+          x_s[ch * PS + L * Wl + pix + 1] = lut[(stg[k] >> (8 * q)) & 255u];
+        }
+      }
+    }
+  }
+  __syncthreads();
+
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int g = lane >> 4, c16 = lane & 15;
+
+  // ---- conv + bias over the band's tile rows inside the image: local tile
+  // row tr is tile row p0 + tr, its patch at staged rows 2 tr .., its outputs
+  // at image rows 2 tr, 2 tr + 1
+  {
+    const int ntr = min(BP + 1, Hp - p0);
+    const int nt = ntr * TX, ng = (nt + 15) >> 4;
+    for (int task = wave; task < ng * NS; task += NW) {
+      const int sl = task / ng, grp = task - sl * ng;
+      const int co0 = 16 * sl;
+      int t = 16 * grp + c16;
+      const bool valid = t < nt;
+      if (!valid) t = 0;
+      const int tr = t / TX, tx = t - tr * TX;
+      F4x4 Ys;
+      if constexpr (CIN == 16) {
+        Ys = wino_tile<1, false, false>(x_s + (2 * tr * Wl + 2 * tx) * PP + 4 * g, Wl * PP, PP,
+                                        U_s + (g * COUT + co0 + c16) * 4, 16 * COUT, 0);
+      } else {
+        // channel g of the tile's 4x4 patch, one MFMA per xi (k = the 4 lane
+        // groups' channels), as wino_conv_pool_kernel
+        const float* xp = x_s + g * PS + 2 * tr * Wl + 2 * tx;
+        const float* up = U_s + g * COUT + co0 + c16;
+        Tile16<float> d;
+#pragma unroll
+        for (int dy = 0; dy < 4; ++dy)
+#pragma unroll
+          for (int dx = 0; dx < 4; ++dx) d.v[4 * dy + dx] = xp[dy * Wl + dx];
+        const Tile16<float> Vs = wino_input_transform(d);
+        f4 acc[16];
+#pragma unroll
+        for (int xi = 0; xi < 16; ++xi) acc[xi] = f4{0.f, 0.f, 0.f, 0.f};
+        float ua[16];
+#pragma unroll
+        for (int xi = 0; xi < 16; ++xi) ua[xi] = up[xi * 4 * COUT];
+#pragma unroll
+        for (int xi = 0; xi < 16; ++xi) acc[xi] = mfma4(ua[xi], Vs.v[xi], acc[xi]);
+        Ys = wino_output_transform(acc);
+      }
+      const f4 bv = *reinterpret_cast<const f4*>(a.bias + co0 + 4 * g);
+      if (valid) {
+#pragma unroll
+        for (int dy = 0; dy < 2; ++dy)
+#pragma unroll
+          for (int dx = 0; dx < 2; ++dx)
+            *reinterpret_cast<f4*>(img + ((2 * tr + dy) * W + 2 * tx + dx) * IPP + co0 + 4 * g) =
+                Ys.v[2 * dy + dx] + bv;
+      }
+    }
+  }
+  __syncthreads();
+
+  // ---- pool: the band's windows (pad-before 0: the tap row H / column W is
+  // padding and skipped), row-major taps, strict >; lanes permuted inside
+  // each 64-element chunk by the conflict-free pool lane map
+  {
+    constexpr float kNegInf = -__builtin_inff();
+    constexpr PoolLaneMap<CQ, IPP> kMap{};
+    const int lmap = kMap.pj[lane] * CQ + kMap.pq[lane];
+    const int ne = min(BP, Hp - p0) * (WP * CQ);
+    for (int e0 = threadIdx.x & ~63; e0 < ne; e0 += NTH) {
+      const int e = e0 + lmap;
+      if (e >= ne) continue;
+      const int pr = e / (WP * CQ), rem = e - pr * (WP * CQ);
+      const int pc = rem / CQ, pq = rem - pc * CQ;
+      f4 best = {kNegInf, kNegInf, kNegInf, kNegInf};
+#pragma unroll
+      for (int dy = 0; dy < 3; ++dy)
+#pragma unroll
+        for (int dx = 0; dx < 3; ++dx) {
+          const int yl = 2 * pr + dy, x = 2 * pc + dx;
+          if (2 * p0 + yl < H && x < W) {
+            const f4 v = *reinterpret_cast<const f4*>(img + (yl * W + x) * IPP + 4 * pq);
+#pragma unroll
+            for (int q = 0; q < 4; ++q)
+              if (v[q] > best[q]) best[q] = v[q];
+          }
+        }
+      const int64_t o = ((static_cast<int64_t>(n) * Hp + p0 + pr) * WP + pc) * COUT + 4 * pq;
+      *reinterpret_cast<f4*>(a.pooled + o) = best;
+    }
+  }
+}
+
+template <int CIN, int COUT, int W, int BP, int NW>
+bool run_head_infer(const HeadArgs& a0, hipStream_t s) {
+  using P = HeadGeo<CIN, COUT, W, BP>;
+  if (t_wino_probe) return true;
+  HeadArgs a = a0;
+  a.nbands = (a.H / 2 + BP - 1) / BP;
+  auto kern = wino_head_infer_kernel<CIN, COUT, W, BP, NW>;
+  allow_lds_w(kern, P::bytes);
+  hipLaunchKernelGGL(kern, dim3(a.N * a.nbands), dim3(64 * NW), P::bytes, s, a);
+  return true;
+}
+
 // Whether both convs of a residual block at this shape run the Winograd
 // forward (the direct kernel they would fall to sums in another order);
 // launches nothing
@@ -3515,6 +3778,76 @@ int wino_stage_form(int N, int H, int W, int C) {
   }
   StageArgs a{};
   return stage_tail_args(a, w, w, y, N, (H + 1) / 2, (W + 1) / 2, C, true, nullptr) ? 1 : 0;
+}
+
+// Pooled rows per workgroup of the inference stage heads (see the table at
+// wino_head_infer_kernel): stage 0 (cin <= 4) at widths 96 / 84 / 128, stage 1
+// (cin 16) at 48 / 42 / 64; 0: no instance
+int wino_head_band(int H, int W, int cin) {
+  if (H < 4 || H % 2 != 0) return 0;
+  if (cin >= 1 && cin <= 4) return W == 96 || W == 84 ? 6 : (W == 128 ? 4 : 0);
+  if (cin == 16) return W == 48 || W == 42 || W == 64 ? 3 : 0;
+  return 0;
+}
+
+namespace {
+
+// The checks of wino_head_infer_launch; with t_wino_probe set nothing runs
+bool head_infer(const void* x, bool is_u8, const float* w, int wcin, const float* b,
+                float* pooled, int N, int H, int W, int Cs, int Cout, hipStream_t s) {
+  if (N < 1 || N > kResBlockMaxFrames || !wino_enabled()) return false;
+  if (wino_head_band(H, W, Cs) == 0) return false;
+  if (static_cast<int64_t>(N) * H * W * (is_u8 ? Cs : 4 * Cs) > kMaxBufBytes) return false;
+  HeadArgs a{};
+  a.x = x; a.w = w; a.bias = b; a.pooled = pooled;
+  a.N = N; a.H = H; a.Cs = Cs; a.wcin = wcin;
+  if (is_u8) {
+    // the launches replaced: frames_f32 and the Winograd conv + pool of the
+    // 4-channel image (tile-row pairs: H % 4 == 0), not the direct conv + pool
+    static const int pool_on = env_knob("SA_F32_WINO_POOL", 7);
+    if (Cs < 1 || Cs > 4 || Cout != 16 || (wcin != Cs && wcin != 4) || (W * Cs) % 4 != 0 ||
+        H % 4 != 0 || !(pool_on & 2))
+      return false;
+    if (W == 96) return run_head_infer<4, 16, 96, 6, 8>(a, s);
+    if (W == 84) return run_head_infer<4, 16, 84, 6, 8>(a, s);
+    return run_head_infer<4, 16, 128, 4, 8>(a, s);
+  }
+  if (Cs != 16 || wcin != 16 || Cout != 32) return false;
+  // the launches replaced compute the conv in Winograd form (the fused conv +
+  // pool, or wino_conv_kernel + maxpool_fwd: bitwise the same pooled values)
+  ConvArgs c{};
+  c.src = x; c.w = w; c.bias = b; c.out = pooled;
+  c.N = N; c.Hs = H; c.Ws = W; c.Cs = Cs;
+  c.Ho = H; c.Wo = W; c.Cout = Cout;
+  c.pt = 1; c.pl = 1; c.D = 1;
+  c.wcin = Cs; c.wcout = Cout;
+  const bool probing = t_wino_probe;
+  t_wino_probe = true;
+  const bool conv = wino_conv_launch(c, false, s);
+  t_wino_probe = probing;
+  if (!conv) return false;
+  if (W == 48) return run_head_infer<16, 32, 48, 3, 12>(a, s);
+  if (W == 42) return run_head_infer<16, 32, 42, 3, 12>(a, s);
+  return run_head_infer<16, 32, 64, 3, 8>(a, s);
+}
+
+}  // namespace
+
+bool wino_head_infer_launch(const void* x, bool is_u8, const float* w, int wcin, const float* b,
+                            float* pooled, int N, int H, int W, int Cs, int Cout,
+                            hipStream_t s) {
+  // dword row loads / 16-B rows
+  if (reinterpret_cast<uintptr_t>(x) % (is_u8 ? 4 : 16) != 0) return false;
+  return head_infer(x, is_u8, w, wcin, b, pooled, N, H, W, Cs, Cout, s);
+}
+
+int wino_head_form(int N, int H, int W, int cin, int cout, bool is_u8) {
+  static const float dummy[4] = {};
+  float* y = const_cast<float*>(dummy);  // geometry checks only: never read or written
+  t_wino_probe = true;
+  const bool ok = head_infer(dummy, is_u8, dummy, cin, dummy, y, N, H, W, cin, cout, nullptr);
+  t_wino_probe = false;
+  return ok ? 1 : 0;
 }
 
 int conv_wino_fault(int v) {

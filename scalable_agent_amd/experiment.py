@@ -168,6 +168,19 @@ def _log_torso_blocks(flags, model):
              'the last stage: head, max-pool and both blocks'
              if form == 'stage' else 'the two blocks of the last stage')
     return
+  if asked == 'heads' and used in ('heads', 'stage', 'fused'):
+    cuda = model.device.type == 'cuda'
+    took = agent.torso_head_form(cuda) or ()
+    form = agent.torso_stage_form(cuda)
+    names = ['stage %d %s' % (s, 'fused (one launch)' if s in took else
+                              'declines (runs as stage)') for s in (0, 1)]
+    log.info('actor inference torso blocks: %s (--torso_blocks=heads on %s '
+             'frames: head of %s; last stage: %s)', used,
+             'x'.join(str(d) for d in agent.frame_shape), ', '.join(names),
+             {'stage': 'head, max-pool and both blocks in one launch',
+              'tail': 'both blocks in one launch'}.get(
+                  form, 'one launch per block'))
+    return
   if asked == used:
     log.info('actor inference torso blocks: %s', used)
     return

@@ -116,7 +116,8 @@ def build_parser() -> argparse.ArgumentParser:
                       'packs the outputs).  Both take up to 63 actions (with '
                       'more the actors sample with torch.multinomial).  bf16 '
                       'inference runs ops.')
-  p.add_argument('--torso_blocks', default='ops', choices=['ops', 'fused', 'stage'],
+  p.add_argument('--torso_blocks', default='ops',
+                 choices=['ops', 'fused', 'stage', 'heads'],
                  help='Residual blocks of the fp32 HIP deep torso in actor '
                       'inference (no autograd, at most 512 frames per launch): '
                       'ops = two Winograd convs per block; fused = ONE kernel '
@@ -124,7 +125,11 @@ def build_parser() -> argparse.ArgumentParser:
                       'head, max-pool and both blocks at an 18x24 input such '
                       'as the 72x96 frame\'s, else its two blocks where the '
                       'whole map fits one workgroup, e.g. 84x84 and 72x128 '
-                      'frames) in ONE kernel.  All three give bitwise the same '
+                      'frames) in ONE kernel; heads = as stage, and the '
+                      'stage-0 and stage-1 heads (conv, bias, max-pool) in ONE '
+                      'kernel each, stage 0 straight from the uint8 frames '
+                      '(72x96, 84x84 and 72x128 frames; other shapes run as '
+                      'stage).  All four give bitwise the same '
                       'features.  bf16 inference fuses its blocks already; '
                       'the shallow torso and the torch backend have nothing '
                       'to fuse and run as with ops.')

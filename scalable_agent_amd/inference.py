@@ -135,7 +135,9 @@ class InferenceModel(object):
 
   @property
   def torso_blocks(self):
-    """The form this model's torso runs: 'stage' (the last stage, or its two
+    """The form this model's torso runs: 'heads' (as 'stage', and the stage-0
+    and / or stage-1 head as one kernel: Agent(torso_blocks='heads') where the
+    head kernel takes the frames), 'stage' (the last stage, or its two
     blocks, in one kernel and every other residual block as one kernel:
     Agent(torso_blocks='stage') where the stage kernel takes the frames),
     'fused' (one kernel per residual block: 'fused', or 'stage' on frames the
@@ -144,6 +146,9 @@ class InferenceModel(object):
     fused = getattr(self.agent, 'torso_blocks_fused', None)
     if fused is None or not fused(cuda):
       return 'ops'
+    heads = getattr(self.agent, 'torso_head_form', None)
+    if heads is not None and heads(cuda):
+      return 'heads'
     form = getattr(self.agent, 'torso_stage_form', None)
     return 'stage' if form is not None and form(cuda) else 'fused'
 

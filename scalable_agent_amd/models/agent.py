@@ -130,8 +130,10 @@ class Agent(nn.Module):
     # (ops/conv_f32.py _DeepTorsoF32Infer) where it applies
     # (torso_blocks_fused); 'stage': the same, and the last stage in one
     # launch where its whole map fits a workgroup (_DeepTorsoF32Stage);
-    # 'ops': two Winograd convs per block
-    if torso_blocks not in ('ops', 'fused', 'stage'):
+    # 'heads': the same, and the stage-0 and stage-1 heads in one launch each
+    # straight from the uint8 frames (_DeepTorsoF32Heads); 'ops': two
+    # Winograd convs per block
+    if torso_blocks not in ('ops', 'fused', 'stage', 'heads'):
       raise ValueError('unknown torso_blocks %r' % (torso_blocks,))
     self.torso_blocks = torso_blocks
     # 'fused': the T = 1 inference step after the torso-FC GEMM is ONE kernel
@@ -533,23 +535,34 @@ class Agent(nn.Module):
             isinstance(generator, PhiloxStream))
 
   def torso_blocks_fused(self, cuda=True):
-    """True when `torso_blocks='fused'` or `'stage'` is honoured for a no-grad
+    """True when `torso_blocks='fused'`, `'stage'` or `'heads'` is honoured for a no-grad
     forward of CUDA frames: HIP backend, deep torso, and the exact-fp32 torso
     kernels run it (the bf16 torso fuses its blocks on its own; the shallow
     torso has none).  Otherwise the torso runs as with 'ops'."""
-    return (self.torso_blocks in ('fused', 'stage') and self.backend == 'hip'
-            and cuda and self.torso_kind == 'deep' and
+    return (self.torso_blocks in ('fused', 'stage', 'heads') and
+            self.backend == 'hip' and cuda and self.torso_kind == 'deep' and
             not _bf16_torso_ready(self))
 
   def torso_stage_form(self, cuda=True):
-    """What `torso_blocks='stage'` runs for the last stage of this agent's
-    frames: 'stage' (head, pool and both blocks in one launch), 'tail' (both
-    blocks in one launch), or None: not asked for, or the torso runs as
-    'fused' / 'ops' there (torso_blocks_fused)."""
-    if self.torso_blocks != 'stage' or not self.torso_blocks_fused(cuda):
+    """What `torso_blocks='stage'` (or `'heads'`, which includes it) runs for
+    the last stage of this agent's frames: 'stage' (head, pool and both
+    blocks in one launch), 'tail' (both blocks in one launch), or None: not
+    asked for, or the torso runs as 'fused' / 'ops' there
+    (torso_blocks_fused)."""
+    if (self.torso_blocks not in ('stage', 'heads') or
+        not self.torso_blocks_fused(cuda)):
       return None
     from ..ops import conv_f32
     return conv_f32.stage_form(self.frame_shape)
+
+  def torso_head_form(self, cuda=True):
+    """Which of the stage-0 / stage-1 heads `torso_blocks='heads'` runs as one
+    launch each on this agent's frames: a tuple of stage numbers, empty where
+    both decline; None: not asked for, or the torso runs as 'ops' there."""
+    if self.torso_blocks != 'heads' or not self.torso_blocks_fused(cuda):
+      return None
+    from ..ops import conv_f32
+    return conv_f32.head_form(self.frame_shape)
 
   def _fused_step(self, actions, env_outputs, core_state, generator, epilogue):
     """The T = 1 actor step with the fused core: torso, the torso-FC GEMM

@@ -183,6 +183,32 @@ class _DeepTorsoF32Stage(_DeepTorsoF32Infer):
     return _deep_forward(None, frames, params, stage=True)
 
 
+class _DeepTorsoF32Heads(_DeepTorsoF32Stage):
+  """Agent(torso_blocks='heads'): as _DeepTorsoF32Stage, and the stage-0 and
+  stage-1 heads are one launch each (cf32_head_fwd: no fp32 image, no argmax,
+  no fix-up launch) where that kernel takes the shape."""
+
+  @staticmethod
+  def forward(ctx, frames, *params):
+    return _deep_forward(None, frames, params, stage=True, heads=True)
+
+
+def head_form(frame_shape, frames=1):
+  """Which of the two first stage heads torso_blocks='heads' runs as one
+  launch (cf32_head_fwd) on frames of this shape: a tuple of the stage numbers
+  (0, 1), empty where both decline and the torso runs as 'stage'.  The
+  launcher's own checks, host arithmetic only."""
+  h, w, c = frame_shape[0], frame_shape[1], frame_shape[2]
+  C = ext()
+  out = []
+  if C.cf32_head_form(frames, h, w, c, 16, True):
+    out.append(0)
+  h, w = (h + 1) // 2, (w + 1) // 2
+  if C.cf32_head_form(frames, h, w, 16, 32, False):
+    out.append(1)
+  return tuple(out)
+
+
 def stage_form(frame_shape, frames=1):
   """What torso_blocks='stage' runs for the last stage of the deep torso on
   frames of this shape: 'stage' (cf32_stage_fwd: head, pool and both blocks),
@@ -194,26 +220,34 @@ def stage_form(frame_shape, frames=1):
   return {2: 'stage', 1: 'tail'}.get(ext().cf32_stage_form(frames, h, w, 32))
 
 
-def _deep_forward(ctx, frames, params, stage=False):
+def _deep_forward(ctx, frames, params, stage=False, heads=False):
   """Forward of the deep torso.  ctx None (_DeepTorsoF32Infer): residual
   blocks run cf32_res_block_fwd (both convs in one launch, t only in LDS,
   bitwise the two launches) where that kernel takes the shape.  stage
   (_DeepTorsoF32Stage): the last stage runs cf32_stage_fwd (head, pool and
   both blocks in one launch), else its two blocks cf32_stage_tail_fwd, where
-  those take the shape; bitwise again."""
+  those take the shape; bitwise again.  heads (_DeepTorsoF32Heads, ctx None):
+  the stage-0 head runs cf32_head_fwd on the uint8 frames and the stage-1
+  head on its fp32 input (one launch each, the pooled map only) where that
+  kernel takes the shape; bitwise the launches replaced."""
   C = ext()
   fused_blocks = ctx is None
+  heads = heads and ctx is None
+  x = frames.contiguous()
+  # heads: stage 0 straight from the uint8 frames; the fp32 image is made
+  # only where that head declines
+  head0 = (C.cf32_head_fwd(x, params[0], params[1])
+           if heads and x.dtype == torch.uint8 else [])
   # stage 0 reads a 4-channel fp32 x / 255 image (one 16-B load per pixel
   # in the conv+pool and scatter-wgrad stagers), or the uint8 frames
-  x = frames.contiguous()
-  if not U8_DIRECT['deep']:
+  if not head0 and not U8_DIRECT['deep']:
     x = C.cf32_frames_f32(x)
   saved, meta = [], []
   p = 0
   for s in range(3):
     w, b = params[p], params[p + 1]
     p += 2
-    if s == 0 and w.shape[2] != x.shape[3]:
+    if s == 0 and not head0 and w.shape[2] != x.shape[3]:
       w = _pad_cin(w, x.shape[3])  # zero rows for the image's pad channel
     H, W = x.shape[1], x.shape[2]
     pbh = layers.same_pads(H, 3, 2)[0]
@@ -223,9 +257,15 @@ def _deep_forward(ctx, frames, params, stage=False):
       if y:
         x = y[0]
         break
-    fused = (C.cf32_wino_conv_pool_fwd(x, w, b) if x.dtype == torch.float32
-             else [])
-    if fused:
+    one = head0 if s == 0 else (
+        C.cf32_head_fwd(x, w, b)
+        if heads and s == 1 and x.dtype == torch.float32 else [])
+    fused = (C.cf32_wino_conv_pool_fwd(x, w, b)
+             if not one and x.dtype == torch.float32 else [])
+    if one:
+      # the inference head: the pooled map only (nothing kept for a backward)
+      xa, arg = one[0], None
+    elif fused:
       # stage 0 (4-channel image -> 16) and stage 1 (16 -> 32) heads
       # with the pool in the Winograd epilogue (the pre-pool map only in
       # LDS); other shapes: the direct conv+pool or conv + maxpool_fwd
@@ -396,12 +436,13 @@ def torso_forward_f32(agent, frames):
   from .conv import FUSED_BLOCK_MAX_FRAMES
   # actor inference (no autograd, a board's worth of frames) of an agent
   # built with torso_blocks='fused': one launch per residual block; 'stage':
-  # and one for the last stage
+  # and one for the last stage; 'heads': and one per stage-0 / stage-1 head
   blocks = getattr(agent, 'torso_blocks', 'ops')
   fn = _DeepTorsoF32
-  if (blocks in ('fused', 'stage') and not torch.is_grad_enabled() and
+  if (blocks in ('fused', 'stage', 'heads') and not torch.is_grad_enabled() and
       frames.shape[0] <= FUSED_BLOCK_MAX_FRAMES):
-    fn = _DeepTorsoF32Stage if blocks == 'stage' else _DeepTorsoF32Infer
+    fn = {'stage': _DeepTorsoF32Stage,
+          'heads': _DeepTorsoF32Heads}.get(blocks, _DeepTorsoF32Infer)
   return _chunked(fn, frames, params)
 
 

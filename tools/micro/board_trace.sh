@@ -3,7 +3,7 @@
 # tools/micro/board_trace.py on the learner process's database; only the
 # summary stays under gpurun_out (the database is larger than gpurun's pull
 # limit).  Extra experiment.py flags follow (e.g. --inference_dtype=fp32
-# --inference_lanes=2 --torso_blocks=ops|fused|stage).
+# --inference_lanes=2 --torso_blocks=ops|fused|stage|heads).
 # usage: board_trace.sh TAG [flags]
 set -e
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/../..}"
