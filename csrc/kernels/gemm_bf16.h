@@ -29,6 +29,19 @@ struct GemmBf16Epilogue {
 int gemm_bf16_splits(int M, int N, int K, int ones_row);
 int64_t gemm_bf16_part_floats(int M, int N, int K, int ones_row, int splits);
 
+// What gemm_bf16_launch decides for a shape - the launcher calls this itself,
+// so a test can assert which program a case runs.  bl: the branch-free
+// buffer-load kernels (false: bounds-checked loads); kchunk: K elements per
+// split, so split z covers [z kchunk, min(K, (z + 1) kchunk)); grid: the GEMM
+// kernel's.  splits <= 0: the count gemm_bf16_splits picks.
+struct GemmBf16LaunchInfo {
+  bool bl;
+  int splits, kchunk;
+  int grid[3];
+};
+GemmBf16LaunchInfo gemm_bf16_info(int M, int N, int K, int lda, int ldb, bool ta, bool tb,
+                                  bool ones_row, int splits = 0);
+
 // C[M, N] (+)= op(A) op(B) over bf16 A / B: op(A)[m, k] = ta ? A[k*lda + m] :
 // A[m*lda + k], op(B)[k, n] = tb ? B[n*ldb + k] : B[k*ldb + n].  lda, ldb
 // multiples of 8 (16-B rows) and 16-B aligned bases; K a multiple of 8 where

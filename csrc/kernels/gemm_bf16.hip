@@ -321,6 +321,28 @@ int gemm_bf16_splits(int M, int N, int K, int ones_row) {
   return s;
 }
 
+// every decision of the launch below (gemm_bf16_info binding: the tests
+// assert the path a shape takes)
+GemmBf16LaunchInfo gemm_bf16_info(int M, int N, int K, int lda, int ldb, bool ta, bool tb,
+                                  bool ones_row, int splits) {
+  GemmBf16LaunchInfo i{};
+  const int Mr = M + (ones_row ? 1 : 0);
+  i.splits = splits > 0 ? splits : gemm_bf16_splits(M, N, K, ones_row);
+  i.kchunk = ((K + i.splits - 1) / i.splits + BK - 1) / BK * BK;
+  i.grid[0] = (Mr + BM - 1) / BM;
+  i.grid[1] = (N + BN - 1) / BN;
+  i.grid[2] = i.splits;
+  // layout-specialised kernels; the branch-free buffer-load form needs whole
+  // 8-element chunks along the M / N-contiguous operands and 32-bit offsets
+  // (SA_GEMM_BL=0: bounds-checked loads)
+  static const int blenv = sa::env_knob("SA_GEMM_BL", 1);
+  const int64_t abytes = (ta ? static_cast<int64_t>(K) * lda : static_cast<int64_t>(M) * lda) * 2;
+  const int64_t bbytes = (tb ? static_cast<int64_t>(N) * ldb : static_cast<int64_t>(K) * ldb) * 2;
+  i.bl = blenv && (!ta || M % 8 == 0) && (tb || N % 8 == 0) && abytes < 0xFFFFFF00ll &&
+         bbytes < 0xFFFFFF00ll;
+  return i;
+}
+
 bool gemm_bf16_launch(const uint16_t* A, const uint16_t* B, int M, int N, int K,
                       int lda, int ldb, bool ta, bool tb, bool ones_row, int splits,
                       float* part, const GemmBf16Epilogue& ep, hipStream_t stream) {
@@ -330,25 +352,19 @@ bool gemm_bf16_launch(const uint16_t* A, const uint16_t* B, int M, int N, int K,
   if (ones_row && ep.colsum == nullptr) return false;
   if (ep.accumulate && ep.c_bf16) return false;
   if (splits > 1 && part == nullptr) return false;
+  const auto li = gemm_bf16_info(M, N, K, lda, ldb, ta, tb, ones_row, std::max(1, splits));
   Args a{};
   a.A = A;
   a.B = B;
   a.M = M; a.N = N; a.K = K; a.lda = lda; a.ldb = ldb;
   a.ta = ta; a.tb = tb; a.ones_row = ones_row;
-  a.splits = std::max(1, splits);
-  a.kchunk = ((K + a.splits - 1) / a.splits + BK - 1) / BK * BK;
+  a.splits = li.splits;
+  a.kchunk = li.kchunk;
   a.part = part;
   a.ep = ep;
   const int Mr = M + (ones_row ? 1 : 0);
-  dim3 grid((Mr + BM - 1) / BM, (N + BN - 1) / BN, a.splits);
-  // layout-specialised kernels; the branch-free buffer-load form needs whole
-  // 8-element chunks along the M / N-contiguous operands and 32-bit offsets
-  // (SA_GEMM_BL=0: bounds-checked loads)
-  static const int blenv = sa::env_knob("SA_GEMM_BL", 1);
-  const int64_t abytes = (ta ? static_cast<int64_t>(K) * lda : static_cast<int64_t>(M) * lda) * 2;
-  const int64_t bbytes = (tb ? static_cast<int64_t>(N) * ldb : static_cast<int64_t>(K) * ldb) * 2;
-  const bool bl = blenv && (!ta || M % 8 == 0) && (tb || N % 8 == 0) && abytes < 0xFFFFFF00ll &&
-                  bbytes < 0xFFFFFF00ll;
+  dim3 grid(li.grid[0], li.grid[1], li.grid[2]);
+  const bool bl = li.bl;
   void (*kern)(Args);
   if (bl)
     kern = ta ? (tb ? gemm_bf16_kernel<true, true, true> : gemm_bf16_kernel<true, false, true>)

@@ -27,6 +27,20 @@ struct GemmEpilogue {
 int gemm_f32_splits(int M, int N, int K, int ones_row);
 int64_t gemm_f32_part_floats(int M, int N, int K, int ones_row, int splits);
 
+// What gemm_f32_launch decides for a shape - the launcher calls this itself,
+// so a test can assert which program a case runs.  bl: the branch-free
+// buffer-load kernel (false: the bounds-checked generic one); kchunk: K
+// elements per split, so split z covers [z kchunk, min(K, (z + 1) kchunk));
+// rm: 32-row MFMA blocks per wave (workgroup tile 64 rm x 64); grid: the GEMM
+// kernel's.  splits <= 0: the count gemm_f32_splits picks.
+struct GemmLaunchInfo {
+  bool bl;
+  int splits, kchunk, rm;
+  int grid[3];
+};
+GemmLaunchInfo gemm_f32_info(int M, int N, int K, int lda, int ldb, bool ta, bool tb,
+                             bool ones_row, int splits = 0);
+
 // C[M, N] (+)= op(A) op(B): op(A)[m, k] = ta ? A[k*lda + m] : A[m*lda + k],
 // op(B)[k, n] = tb ? B[n*ldb + k] : B[k*ldb + n].  lda, ldb, K multiples of
 // 4 and 16-B aligned bases (false otherwise, nothing launched).

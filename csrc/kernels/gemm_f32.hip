@@ -449,6 +449,28 @@ int gemm_f32_splits(int M, int N, int K, int ones_row) {
   return s;
 }
 
+// every decision of the launch below (gemm_f32_info binding: the tests assert
+// the path a shape takes)
+GemmLaunchInfo gemm_f32_info(int M, int N, int K, int lda, int ldb, bool ta, bool tb,
+                             bool ones_row, int splits) {
+  GemmLaunchInfo i{};
+  const int Mr = M + (ones_row ? 1 : 0);
+  i.splits = splits > 0 ? splits : gemm_f32_splits(M, N, K, ones_row);
+  i.kchunk = ((K + i.splits - 1) / i.splits + BK - 1) / BK * BK;
+  i.rm = gemm_rm(Mr);
+  i.grid[0] = (Mr + BM * i.rm - 1) / (BM * i.rm);
+  i.grid[1] = (N + BN - 1) / BN;
+  i.grid[2] = i.splits;
+  // branch-free buffer-load variant (SA_GEMM_BL=0: the generic kernel):
+  // whole quads along every f4 operand axis, byte offsets within 32 bits
+  static const int bl = sa::env_knob("SA_GEMM_BL", 1);
+  const int64_t abytes = (ta ? static_cast<int64_t>(K) * lda : static_cast<int64_t>(M) * lda) * 4;
+  const int64_t bbytes = (tb ? static_cast<int64_t>(N) * ldb : static_cast<int64_t>(K) * ldb) * 4;
+  i.bl = bl && (!ta || M % 4 == 0) && (tb || N % 4 == 0) && abytes < 0xFFFFFF00ll &&
+         bbytes < 0xFFFFFF00ll;
+  return i;
+}
+
 bool gemm_f32_launch(const float* A, const float* B, int M, int N, int K, int lda,
                      int ldb, bool ta, bool tb, bool ones_row, int splits, float* part,
                      const GemmEpilogue& ep, hipStream_t stream) {
@@ -458,25 +480,20 @@ bool gemm_f32_launch(const float* A, const float* B, int M, int N, int K, int ld
   if (lda % 4 || ldb % 4 || (K % 4 && (!ta || tb))) return false;
   if (ones_row && ep.colsum == nullptr) return false;
   if (splits > 1 && part == nullptr) return false;
+  const auto li = gemm_f32_info(M, N, K, lda, ldb, ta, tb, ones_row, std::max(1, splits));
   Args a{};
   a.A = A;
   a.B = B;
   a.M = M; a.N = N; a.K = K; a.lda = lda; a.ldb = ldb;
   a.ta = ta; a.tb = tb; a.ones_row = ones_row;
-  a.splits = std::max(1, splits);
-  a.kchunk = ((K + a.splits - 1) / a.splits + BK - 1) / BK * BK;
+  a.splits = li.splits;
+  a.kchunk = li.kchunk;
   a.part = part;
   a.ep = ep;
   const int Mr = M + (ones_row ? 1 : 0);
-  const int rm = gemm_rm(Mr);
-  dim3 grid((Mr + BM * rm - 1) / (BM * rm), (N + BN - 1) / BN, a.splits);
-  // branch-free buffer-load variant (SA_GEMM_BL=0: the generic kernel):
-  // whole quads along every f4 operand axis, byte offsets within 32 bits
-  static const int bl = sa::env_knob("SA_GEMM_BL", 1);
-  const int64_t abytes = (ta ? static_cast<int64_t>(K) * lda : static_cast<int64_t>(M) * lda) * 4;
-  const int64_t bbytes = (tb ? static_cast<int64_t>(N) * ldb : static_cast<int64_t>(K) * ldb) * 4;
-  if (bl && (!ta || M % 4 == 0) && (tb || N % 4 == 0) && abytes < 0xFFFFFF00ll &&
-      bbytes < 0xFFFFFF00ll) {
+  const int rm = li.rm;
+  dim3 grid(li.grid[0], li.grid[1], li.grid[2]);
+  if (li.bl) {
     auto k = rm == 2
                  ? (ta ? (tb ? gemm_f32_bl_kernel<2, true, true> : gemm_f32_bl_kernel<2, true, false>)
                        : (tb ? gemm_f32_bl_kernel<2, false, true>

@@ -709,6 +709,36 @@ void register_learner_ops(pybind11::module& m) {
         pybind11::arg("accumulate") = false, pybind11::arg("colsum") = pybind11::none(),
         pybind11::arg("aug_reward") = pybind11::none(),
         pybind11::arg("aug_action") = pybind11::none());
+  // read-only: the path gemm_f32 / gemm_bf16 take for a shape (the launchers'
+  // own decision functions)
+  m.def("gemm_f32_info", [](int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldb, bool ta,
+                            bool tb, bool ones_row) {
+          TORCH_CHECK(M > 0 && N > 0 && K > 0, "gemm_f32_info: empty product");
+          const sa::GemmLaunchInfo i = sa::gemm_f32_info(M, N, K, lda, ldb, ta, tb, ones_row);
+          pybind11::dict d;
+          d["bl"] = i.bl;
+          d["splits"] = i.splits;
+          d["kchunk"] = i.kchunk;
+          d["rm"] = i.rm;
+          d["grid"] = pybind11::make_tuple(i.grid[0], i.grid[1], i.grid[2]);
+          return d;
+        }, pybind11::arg("M"), pybind11::arg("N"), pybind11::arg("K"), pybind11::arg("lda"),
+        pybind11::arg("ldb"), pybind11::arg("ta"), pybind11::arg("tb"),
+        pybind11::arg("ones_row"));
+  m.def("gemm_bf16_info", [](int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldb, bool ta,
+                             bool tb, bool ones_row) {
+          TORCH_CHECK(M > 0 && N > 0 && K > 0, "gemm_bf16_info: empty product");
+          const sa::GemmBf16LaunchInfo i =
+              sa::gemm_bf16_info(M, N, K, lda, ldb, ta, tb, ones_row);
+          pybind11::dict d;
+          d["bl"] = i.bl;
+          d["splits"] = i.splits;
+          d["kchunk"] = i.kchunk;
+          d["grid"] = pybind11::make_tuple(i.grid[0], i.grid[1], i.grid[2]);
+          return d;
+        }, pybind11::arg("M"), pybind11::arg("N"), pybind11::arg("K"), pybind11::arg("lda"),
+        pybind11::arg("ldb"), pybind11::arg("ta"), pybind11::arg("tb"),
+        pybind11::arg("ones_row"));
   m.def("colsum_f32_", &colsum_f32_);
   m.def("relu_bwd_colsum_", &relu_bwd_colsum_, pybind11::arg("dy"),
         pybind11::arg("y"), pybind11::arg("out") = pybind11::none());

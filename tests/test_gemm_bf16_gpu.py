@@ -68,6 +68,13 @@ def test_gemm_bf16_plain(cuda, M, N, K, ta, tb):
   assert _rel(C16, ref) <= 8e-3
 
 
+@pytest.mark.parametrize('M,N,K', [(36, 44, 24), (8, 4, 8), (101, 70, 136), (45, 9, 16)])
+def test_gemm_bf16_plain_both_transposed(cuda, M, N, K):
+  """(ta, tb) = (True, True) at the small shapes: no learner product uses
+  it, the bindings accept it and every variant compiles it."""
+  test_gemm_bf16_plain(cuda, M, N, K, True, True)
+
+
 def test_gemm_bf16_fc_epilogue(cuda):
   """h_aug = [relu(feats W + b), clip(r), one_hot(a), 0...] in bf16."""
   g = torch.Generator().manual_seed(1)

@@ -45,6 +45,13 @@ def test_gemm_f32_plain(cuda, M, N, K, ta, tb):
   assert _rel(C, ref) <= 2e-6
 
 
+@pytest.mark.parametrize('M,N,K', [(36, 44, 28), (8, 4, 4)])
+def test_gemm_f32_plain_both_transposed(cuda, M, N, K):
+  """(ta, tb) = (True, True) at the small shapes: no learner product uses
+  it, the bindings accept it and every variant compiles it."""
+  test_gemm_f32_plain(cuda, M, N, K, True, True)
+
+
 def test_gemm_f32_fc_epilogue(cuda):
   """relu(feats W + b) with the [clip(r), one_hot(a), 0...] columns."""
   g = torch.Generator().manual_seed(1)
