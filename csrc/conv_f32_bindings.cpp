@@ -649,6 +649,21 @@ void register_conv_f32_ops(pybind11::module& m) {
   m.def("cf32_wino_keep_launches", []() { return sa::cf32::conv_wino_keep_launches(); });
   // R CUs per XCD left out of every persistent conv grid (-1 reads)
   m.def("cf32_cu_reserve", [](int r) { return sa::cf32::conv_cu_reserve(r); });
+  // test hooks: cap on the persistent direct grids' x dimension (0 = none,
+  // < 0 reads; returns the previous value), and the last direct launch on
+  // this host thread (reset: family becomes "none" afterwards)
+  m.def("cf32_grid_cap", [](int n) { return sa::cf32::conv_grid_cap(n); });
+  m.def("cf32_launch_info", [](bool reset) {
+    const sa::cf32::LaunchInfo i = sa::cf32::conv_launch_info(reset);
+    pybind11::dict d;
+    d["family"] = std::string(i.family);
+    d["grid_x"] = i.grid_x;
+    d["grid_y"] = i.grid_y;
+    d["ntiles"] = i.ntiles;
+    d["rows"] = i.rows;
+    d["tiles_per_img"] = i.tiles_per_img;
+    return d;
+  }, arg("reset") = false);
   // deferred weight-gradient reductions: defer(True) ... flush() -> one launch
   m.def("cf32_wgrad_defer", [](bool on) {
     t_defer = on;

@@ -119,6 +119,24 @@ int64_t conv_wino_keep_launches();
 int conv_cu_reserve(int r);
 // CUs the persistent grids are sized for now: 256 - 8 * conv_cu_reserve(-1).
 int conv_cus();
+// Test hook: caps the x dimension of the persistent grids of the direct
+// kernels (conv_fwd, conv_pool_fwd, conv_wgrad, pool_wgrad) at n workgroups,
+// so a handful of images gives every workgroup several tiles; for the two
+// weight-gradient kernels the capped grid is also the slot count of the
+// reduction.  0 = no cap (the default: every launch is what it is without
+// the hook); n < 0 reads.  Returns the previous value.  Launch-time state
+// like conv_cu_reserve, not read from the environment.
+int conv_grid_cap(int n);
+// Test hook: the last launch of a direct kernel on this host thread.
+// family: conv_fwd, conv_pool_fwd, conv_wgrad, pool_wgrad, maxpool_bwd_blk,
+// maxpool_bwd, frames_tile, frames, or none (nothing since the last reset:
+// the Winograd launchers took the calls).  rows = R (output / pooled rows per
+// tile); ntiles, rows and tiles_per_img are 0 for the non-persistent kernels.
+struct LaunchInfo {
+  const char* family;
+  int grid_x, grid_y, ntiles, rows, tiles_per_img;
+};
+LaunchInfo conv_launch_info(bool reset);
 bool wino_conv_launch(const ConvArgs& a, bool flip, hipStream_t s);
 // Whole residual block for actor inference (conv_wino.hip
 // wino_res_block_kernel), C = 16 or 32, fp32 NHWC:

@@ -53,6 +53,29 @@ int conv_cu_reserve(int r) {
 int conv_cus() { return 256 - 8 * conv_cu_reserve(-1); }
 
 namespace {
+int g_grid_cap = 0;  // 0: no cap (conv_grid_cap)
+thread_local LaunchInfo t_launch = {"none", 0, 0, 0, 0, 0};
+
+// persistent grid width after the test cap (identity at the default 0)
+int capped(int G) { return g_grid_cap > 0 ? std::min(G, g_grid_cap) : G; }
+void note_launch(const char* family, int gx, int gy, int ntiles, int rows, int tpi) {
+  t_launch = LaunchInfo{family, gx, gy, ntiles, rows, tpi};
+}
+}  // namespace
+
+int conv_grid_cap(int n) {
+  const int old = g_grid_cap;
+  if (n >= 0) g_grid_cap = n;
+  return old;
+}
+
+LaunchInfo conv_launch_info(bool reset) {
+  const LaunchInfo i = t_launch;
+  if (reset) t_launch = LaunchInfo{"none", 0, 0, 0, 0, 0};
+  return i;
+}
+
+namespace {
 
 typedef float f4 __attribute__((ext_vector_type(4)));
 typedef float f2 __attribute__((ext_vector_type(2)));
@@ -1521,9 +1544,10 @@ bool run_conv(const ConvArgs& a, hipStream_t s) {
   static const int occ_env = sa::measure_knob("SA_F32_FWD_OCC", 0);
   const int occ_cap = occ_env ? occ_env : (CINP <= 16 && COUT_T <= 16 ? 3 : 2);
   const int per_cu = occupancy(bytes(R), occ_cap);
-  const int G = std::max(1, std::min(ntiles, conv_cus() * per_cu / gy));
+  const int G = capped(std::max(1, std::min(ntiles, conv_cus() * per_cu / gy)));
   auto kern = conv_fwd_kernel<CINP, COUT_T, K, S, SRC, FLIP>;
   allow_lds(kern, bytes(R));
+  note_launch("conv_fwd", G, gy, ntiles, R, nt);
   hipLaunchKernelGGL(kern, dim3(G, gy), dim3(kThreads), bytes(R), s, a, R, nt, ntiles);
   return true;
 }
@@ -1553,9 +1577,10 @@ bool run_conv_pool(const ConvArgs& a, int pbh, int pbw, float* pooled, uint8_t* 
   const int ntiles = a.N * nt;
   static const int occ_cap = sa::measure_knob("SA_F32_POOL_OCC", 3);
   const int per_cu = occupancy(bytes(R), occ_cap);
-  const int G = std::max(1, std::min(ntiles, conv_cus() * per_cu));
+  const int G = capped(std::max(1, std::min(ntiles, conv_cus() * per_cu)));
   auto kern = conv_pool_fwd_kernel<CINP, COUT, SRC>;
   allow_lds(kern, bytes(R));
+  note_launch("conv_pool_fwd", G, 1, ntiles, R, nt);
   hipLaunchKernelGGL(kern, dim3(G), dim3(kThreads), bytes(R), s, a, R, nt, ntiles, pbh, pbw,
                      Hp, Wp, pooled, arg);
   return true;
@@ -1596,10 +1621,11 @@ bool run_wgrad(const WgradArgs& a, float* ws, hipStream_t s) {
   const int R = (a.Ho + nt - 1) / nt;
   const int ntiles = a.N * nt;
   const int ngrp = a.Cout / CG;
-  const int G = static_cast<int>(
-      std::min<int64_t>(ntiles, wgrad_slots(K, CINP, a.Cout)));
+  const int G = capped(static_cast<int>(
+      std::min<int64_t>(ntiles, wgrad_slots(K, CINP, a.Cout))));
   auto kern = conv_wgrad_kernel<CINP, K, S, SRC, NTT, WSM, GATHER>;
   allow_lds(kern, bytes(R));
+  note_launch("conv_wgrad", G, ngrp, ntiles, R, nt);
   hipLaunchKernelGGL(kern, dim3(G, ngrp), dim3(kThreads), bytes(R), s, a, R, nt, ntiles, ws);
   wgrad_reduce(ws, G, ngrp, MT * 16, CG, CINP, M, a.dw_cin > 0 ? a.dw_cin : a.Cin, a.Cout,
                a.dw, a.db, s);
@@ -1715,7 +1741,8 @@ static bool run_pool_wgrad(const WgradArgs& a, float* ws, int u8_cs, hipStream_t
   const int tpi = (pg.Hp + kPwRows - 1) / kPwRows;
   const int ntiles = a.N * tpi;
   static const int slots = std::max(1, std::min(kPwSlots, sa::measure_knob("SA_F32_PW_SLOTS", kPwSlots)));
-  const int G = std::min(ntiles, slots);
+  const int G = capped(std::min(ntiles, slots));
+  note_launch("pool_wgrad", G, 1, ntiles, kPwRows, tpi);
   size_t lds = std::max<size_t>(sizeof(float) * 4 * (2 * kPwRows + 3) * pw_pitch(a.W),
                                 sizeof(float) * 4 * 37 * 16);
   if (u8_cs > 0) {
@@ -1805,12 +1832,14 @@ bool maxpool_bwd_launch(const float* dy, const uint8_t* arg, float* dx, int N, i
   if (blk && pb_h == 0 && pb_w == 0 && H == 2 * Hp && W == 2 * Wp) {
     const int64_t total = static_cast<int64_t>(N) * Hp * (static_cast<int64_t>(Wp) << sh);
     if (total < (int64_t{1} << 31)) {
+      note_launch("maxpool_bwd_blk", static_cast<int>((total + 255) / 256), 1, 0, 0, 0);
       hipLaunchKernelGGL(maxpool_bwd_blk_kernel, dim3(static_cast<unsigned>((total + 255) / 256)),
                          dim3(256), 0, s, dy, arg, dx, N, Hp, Wp, C, sh);
       return true;
     }
   }
   const dim3 grid(static_cast<unsigned>(N) * H, ((W << sh) + 255) / 256);
+  note_launch("maxpool_bwd", static_cast<int>(grid.x), static_cast<int>(grid.y), 0, 0, 0);
   hipLaunchKernelGGL(maxpool_bwd_kernel, grid, dim3(256), 0, s, dy, arg, dx, N, H, W, C, Hp,
                      Wp, pb_h, pb_w, sh);
   return true;
@@ -1820,12 +1849,14 @@ void frames_f32_launch(const uint8_t* x, float* y, int64_t P, int Cs, hipStream_
   static const bool tiled = sa::env_knob("SA_FRAMES_TILE", 1) != 0;  // 0: one pixel per thread
   if (tiled && (reinterpret_cast<uintptr_t>(x) & 3) == 0 && Cs >= 1 && Cs <= 4) {
     const int64_t blocks = std::max<int64_t>(1, std::min<int64_t>((P + 1023) / 1024, 8192));
+    note_launch("frames_tile", static_cast<int>(blocks), 1, 0, 0, 0);
     hipLaunchKernelGGL(frames_f32_tile_kernel, dim3(blocks), dim3(256), 0, s, x,
                        reinterpret_cast<f4*>(y), P, Cs);
     return;
   }
   int64_t blocks = std::min<int64_t>((P + 255) / 256, 8192);
   if (blocks < 1) blocks = 1;
+  note_launch("frames", static_cast<int>(blocks), 1, 0, 0, 0);
   hipLaunchKernelGGL(frames_f32_kernel, dim3(blocks), dim3(256), 0, s, x,
                      reinterpret_cast<f4*>(y), P, Cs);
 }
