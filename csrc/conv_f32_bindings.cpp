@@ -664,6 +664,25 @@ void register_conv_f32_ops(pybind11::module& m) {
     d["tiles_per_img"] = i.tiles_per_img;
     return d;
   }, arg("reset") = false);
+  // the same two hooks for the persistent Winograd kernels (conv_wino.hip):
+  // a cap of their own on the grid (for the weight-gradient launchers also
+  // the slot count), and the last Winograd launch on this host thread
+  m.def("cf32_wino_grid_cap", [](int n) { return sa::cf32::conv_wino_grid_cap(n); });
+  m.def("cf32_wino_launch_info", [](bool reset) {
+    const sa::cf32::WinoLaunchInfo i = sa::cf32::conv_wino_launch_info(reset);
+    pybind11::dict d;
+    d["family"] = std::string(i.family);
+    d["cin"] = i.cin;
+    d["cout"] = i.cout;
+    d["grid"] = i.grid;
+    d["nranges"] = i.nranges;
+    d["rt"] = i.rt;
+    d["tiles_per_img"] = i.tiles_per_img;
+    d["geo"] = i.geo;
+    d["fl"] = i.fl;
+    d["flip"] = i.flip;
+    return d;
+  }, arg("reset") = false);
   // deferred weight-gradient reductions: defer(True) ... flush() -> one launch
   m.def("cf32_wgrad_defer", [](bool on) {
     t_defer = on;

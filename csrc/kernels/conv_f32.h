@@ -137,6 +137,33 @@ struct LaunchInfo {
   int grid_x, grid_y, ntiles, rows, tiles_per_img;
 };
 LaunchInfo conv_launch_info(bool reset);
+// Test hook: caps the grids of the persistent Winograd kernels (conv_wino.hip:
+// the forward / data gradient, the stage heads with the pool - the fix-up
+// grid and the `side` split follow - the whole-image head, the weight
+// gradient and both fused backward kernels) at n workgroups, so a handful of
+// images gives every workgroup a run of several ranges; in the three
+// weight-gradient launchers the capped grid is also the slot count of the
+// reduction.  Same contract as conv_grid_cap and independent of it: 0 = no
+// cap (the default: every launch is what it is without the hook), n < 0
+// reads, returns the previous value, launch-time state, not read from the
+// environment.
+int conv_wino_grid_cap(int n);
+// Test hook: the last launch of a persistent Winograd kernel on this host
+// thread (conv_launch_info does not see these).  family: wino_conv,
+// wino_pool, wino_pool_ot (odd tile rows), wino_pool_img, wino_wgrad,
+// wino_bwd16, wino_bwd32, wino_bwd32_keep, or none (nothing since the last
+// reset).  rt = tiles per range (the pool heads: one tile-row pair = W tiles;
+// wino_pool_img: the image's tiles); geo = 1 for a compile-time-geometry
+// instance (GH x GW; wino_pool_img), 0 for runtime geometry; fl = the
+// instance's compile-time flags in the forward's bit order (1 ReLU on the
+// input, 2 ReLU on the output, 4 mask, 8 add, 16 bias; the backward kernels
+// report their compile-time ReLU / mask bits), -1 where the flags are
+// arguments; flip = 1 for the data gradient.
+struct WinoLaunchInfo {
+  const char* family;
+  int cin, cout, grid, nranges, rt, tiles_per_img, geo, fl, flip;
+};
+WinoLaunchInfo conv_wino_launch_info(bool reset);
 bool wino_conv_launch(const ConvArgs& a, bool flip, hipStream_t s);
 // Whole residual block for actor inference (conv_wino.hip
 // wino_res_block_kernel), C = 16 or 32, fp32 NHWC:

@@ -505,6 +505,18 @@ void allow_lds_w(Kern k, size_t bytes) {
 
 int g_wino_fault = 0;  // conv_wino_fault(): tests of the fail-loud hand-off
 
+// Test hooks (conv_f32.h): the grid cap of the persistent launchers below and
+// the record of the last launch.  Host-side only; with the cap at 0 wino_cap
+// is the identity.
+int g_wino_grid_cap = 0;
+thread_local WinoLaunchInfo t_wino_launch = {"none", 0, 0, 0, 0, 0, 0, 0, -1, 0};
+int wino_cap(int G) { return g_wino_grid_cap > 0 ? std::min(G, g_wino_grid_cap) : G; }
+void note_wino(const char* family, int cin, int cout, int grid, int nranges, int rt, int tpi,
+               bool geo, int fl, bool flip) {
+  t_wino_launch = WinoLaunchInfo{family, cin, cout, grid, nranges, rt, tpi, geo ? 1 : 0, fl,
+                                 flip ? 1 : 0};
+}
+
 // While set, run_wino_g answers whether it would run the shape and launches
 // nothing (wino_res_block_launch: the fused block declines exactly where
 // either conv of the two-launch form would leave the Winograd forward).
@@ -559,9 +571,10 @@ bool run_wino_g(const ConvArgs& c, bool flip, hipStream_t s) {
   const int per_cu = std::max(1, std::min(WPS * 4 / NW, static_cast<int>((160 * 1024) / (bytes + 256))));
   static const int occ_env = measure_knob("SA_WINO_OCC", 0);
   const int occ = occ_env > 0 ? std::min(occ_env, per_cu) : per_cu;
-  const int G = std::max(1, std::min(a.nranges, conv_cus() * occ));
+  const int G = wino_cap(std::max(1, std::min(a.nranges, conv_cus() * occ)));
   auto kern = wino_conv_kernel<CIN, COUT, NH, NW, RT, MAXC, WPS, FL, GH, GW>;
   allow_lds_w(kern, bytes);
+  note_wino("wino_conv", CIN, COUT, G, a.nranges, RT, per_img, GH > 0, FL, flip);
   hipLaunchKernelGGL(kern, dim3(G), dim3(64 * NW), bytes, s, a);
   return true;
 }
@@ -986,6 +999,10 @@ __global__ __launch_bounds__((64 * PoolGeo<CIN, COUT, RT>::NW), 3) void wino_con
         if (cvalid) {
           *reinterpret_cast<f4*>(pa.pooled + cdst) = best;
           *reinterpret_cast<uint32_t*>(pa.arg + cdst) = pack_codes(code);
+          // an odd-TY image's last range has no (c) below to reset the carry:
+          // left set, the next image's first range of the same run would merge
+          // its row 0 into this window and store it again
+          if constexpr (OT) cvalid = false;
         } else {  // the run's first range: the previous workgroup holds rows 4k-2, 4k-1
           // (indexed by (pj, pq): wino_pool_fix_kernel's thread numbering)
           pa.side_v[blockIdx.x * (WP * CQ) + pj * CQ + pq] = best;
@@ -1095,7 +1112,7 @@ bool run_wino_pool(const float* x, const float* w, const float* b, float* pooled
   static const int occ = measure_knob("SA_WINO_POOL_OCC", 0);
   const int lds_cu = static_cast<int>((160 * 1024) / (P::bytes + 256));
   const int per_cu = std::max(1, std::min(occ > 0 ? occ : 3 * 4 / P::NW, lds_cu));
-  const int G = std::max(1, std::min(a.nranges, conv_cus() * per_cu));
+  const int G = wino_cap(std::max(1, std::min(a.nranges, conv_cus() * per_cu)));
   const int side_n = (W / 2) * P::CQ;
   if (static_cast<int64_t>(G) * side_n * 5 > side_floats) return false;
   WinoPoolArgs pa{};
@@ -1110,6 +1127,8 @@ bool run_wino_pool(const float* x, const float* w, const float* b, float* pooled
   auto kern = TY % 2 != 0 ? wino_conv_pool_kernel<CIN, COUT, RT, kHasOT>
                           : wino_conv_pool_kernel<CIN, COUT, RT>;
   allow_lds_w(kern, P::bytes);
+  note_wino(TY % 2 != 0 ? "wino_pool_ot" : "wino_pool", CIN, COUT, G, a.nranges, RT, TY * TX,
+            false, -1, false);
   hipLaunchKernelGGL(kern, dim3(G), dim3(64 * P::NW), P::bytes, s, pa);
   hipLaunchKernelGGL(wino_pool_fix_kernel, dim3(G), dim3(256), 0, s, pa.side_v, pa.side_c,
                      pooled, arg, a.nranges, (TY + 1) / 2, TY, W / 2, COUT);
@@ -1314,9 +1333,10 @@ bool run_wino_pool_img(const float* x, const float* w, const float* b, float* po
   a.N = N; a.H = H; a.W = W;
   a.nranges = N;
   a.runs = 1;
-  const int G = std::max(1, std::min(N, conv_cus()));
+  const int G = wino_cap(std::max(1, std::min(N, conv_cus())));
   auto kern = wino_conv_pool_img_kernel<CIN, COUT, H, W>;
   allow_lds_w(kern, P::bytes);
+  note_wino("wino_pool_img", CIN, COUT, G, N, P::NTI, P::NTI, true, -1, false);
   WinoPoolArgs pa{};
   pa.c = a;
   pa.pooled = pooled;
@@ -1682,7 +1702,7 @@ bool run_wino_wgrad(const WgradArgs& c, float* ws, hipStream_t s) {
   const int nranges = static_cast<int>((NT + RT - 1) / RT);
   // slots: one per resident workgroup (<= the direct kernel's workspace)
   const int64_t cap = wgrad_workspace_floats(3, CIN, COUT) / (static_cast<int64_t>(rows16) * COUT);
-  const int G = static_cast<int>(std::min<int64_t>({nranges, conv_cus(), cap}));
+  const int G = wino_cap(static_cast<int>(std::min<int64_t>({nranges, conv_cus(), cap})));
   WinoWgArgs a{};
   a.x = static_cast<const float*>(c.src);
   a.dy = c.dy;
@@ -1695,6 +1715,7 @@ bool run_wino_wgrad(const WgradArgs& c, float* ws, hipStream_t s) {
   a.relu_in = c.relu_in;
   auto kern = wino_wgrad_kernel<CIN, COUT, XR, RT, MAXCX, MAXCD>;
   allow_lds_w(kern, bytes);
+  note_wino("wino_wgrad", CIN, COUT, G, nranges, RT, per_img, false, -1, false);
   hipLaunchKernelGGL(kern, dim3(G), dim3(256), bytes, s, a);
   wgrad_reduce_slots(ws, G, rows16, COUT, CIN, c.dw, c.db, s);
   return true;
@@ -2787,7 +2808,7 @@ bool run_wino_bwd32_g(const float* dy, const float* w, const float* x, const flo
   const int rows16 = ((9 * CX + 16) / 16) * 16;
   const int nranges = static_cast<int>((NT + RT - 1) / RT);
   const int64_t cap = ws_floats / (static_cast<int64_t>(rows16) * CY);
-  const int G = static_cast<int>(std::min<int64_t>({nranges, conv_cus(), cap}));
+  const int G = wino_cap(static_cast<int>(std::min<int64_t>({nranges, conv_cus(), cap})));
   if (G < 1) return false;
   WinoBwdArgs a{};
   a.dy = dy; a.w = w; a.x = x; a.add = add; a.out = out; a.part = ws;
@@ -2815,8 +2836,11 @@ bool run_wino_bwd32_g(const float* dy, const float* w, const float* x, const flo
   const int krows = std::min({KCY * 512 / (Wl * (CY / 4)), KCX * 512 / (Wl * (CX / 4)),
                               maxrows - 1});
   const size_t kbytes = bytes + fused32_keep_lds(RT, maxrows);
-  if (wino_keep_enabled() && kbytes <= 160 * 1024 &&
-      fused32_keep_fits(RT, H, TX, TY, NT, nranges, maxrows, krows)) {
+  const bool keep = wino_keep_enabled() && kbytes <= 160 * 1024 &&
+                    fused32_keep_fits(RT, H, TX, TY, NT, nranges, maxrows, krows);
+  note_wino(keep ? "wino_bwd32_keep" : "wino_bwd32", CX, CY, G, nranges, RT, per_img, GH > 0,
+            (RELU ? 1 : 0) | (MASK ? 4 : 0), true);
+  if (keep) {
     auto kern = wino_bwd_fused32_kernel<CX, CY, RT, KCX, KCY, RELU, MASK, GH, GW, true>;
     allow_lds_w(kern, kbytes);
     hipLaunchKernelGGL(kern, dim3(G), dim3(512), kbytes, s, a);
@@ -2890,7 +2914,7 @@ bool run_wino_bwd_g(const float* dy, const float* w, const float* x, const float
   const int rows16 = ((9 * C + 16) / 16) * 16;
   const int nranges = static_cast<int>((NT + RT - 1) / RT);
   const int64_t cap = ws_floats / (static_cast<int64_t>(rows16) * C);
-  const int G = static_cast<int>(std::min<int64_t>({nranges, conv_cus(), cap}));
+  const int G = wino_cap(static_cast<int>(std::min<int64_t>({nranges, conv_cus(), cap})));
   if (G < 1) return false;
   WinoBwdArgs a{};
   a.dy = dy; a.w = w; a.x = x; a.add = add; a.out = out; a.part = ws;
@@ -2907,6 +2931,7 @@ bool run_wino_bwd_g(const float* dy, const float* w, const float* x, const float
   auto kern = relu_x ? wino_bwd_fused_kernel<C, RT, MAXC, KD, WWG, true, NW, GH, GW>
                      : wino_bwd_fused_kernel<C, RT, MAXC, KD, WWG, false, NW, GH, GW>;
   allow_lds_w(kern, bytes);
+  note_wino("wino_bwd16", C, C, G, nranges, RT, per_img, GH > 0, (relu_x ? 1 : 0) | 4, true);
   hipLaunchKernelGGL(kern, dim3(G), dim3(64 * NW), bytes, s, a);
   wgrad_reduce_slots(ws, G, rows16, C, C, dw, db, s);
   return true;
@@ -3869,6 +3894,18 @@ int conv_wino_keep(int v) {
 }
 
 int64_t conv_wino_keep_launches() { return g_wino_keep_launches; }
+
+int conv_wino_grid_cap(int n) {
+  const int old = g_wino_grid_cap;
+  if (n >= 0) g_wino_grid_cap = n;
+  return old;
+}
+
+WinoLaunchInfo conv_wino_launch_info(bool reset) {
+  const WinoLaunchInfo i = t_wino_launch;
+  if (reset) t_wino_launch = WinoLaunchInfo{"none", 0, 0, 0, 0, 0, 0, 0, -1, 0};
+  return i;
+}
 
 bool wino_enabled() {
   static const bool on = env_knob("SA_F32_WINO", 1) != 0;
