@@ -633,7 +633,12 @@ std::vector<at::Tensor> lang_lstm_bwd(at::Tensor lengths, at::Tensor kernel, at:
                                       c10::optional<at::Tensor> egrad) {
   LB_CHECK(lengths); LB_CHECK(kernel); LB_CHECK(dout); LB_CHECK(acts); LB_CHECK(cs);
   LB_F32(dout); LB_F32(acts); LB_F32(cs); LB_F32(kernel);
+  TORCH_CHECK(kernel.dim() == 2 && kernel.size(0) == 84 && kernel.size(1) == 256,
+              "language LSTM kernel [84, 256]");
+  TORCH_CHECK(acts.dim() == 3 && acts.size(2) == 256, "acts [L, N, 256]");
   const int L = acts.size(0), N = acts.size(1);
+  TORCH_CHECK(cs.dim() == 3 && cs.size(0) == L && cs.size(1) == N && cs.size(2) == 64,
+              "cs [L, N, 64]");
   TORCH_CHECK(dout.numel() == static_cast<int64_t>(N) * 64, "dout [N, 64]");
   TORCH_CHECK(lengths.scalar_type() == at::kLong && lengths.numel() == N, "lengths [N] int64");
   const bool fused = egrad.has_value() && egrad->defined();
