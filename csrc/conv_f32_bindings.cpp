@@ -581,6 +581,45 @@ at::Tensor frames_f32(at::Tensor x) {
   return y;
 }
 
+// The whole shallow conv torso (actor inference) in one launch
+// (conv_f32.hip shallow_torso_kernel): uint8 frames [N,H,W,C], the UNPADDED
+// w1 [8,8,C,32], w2 [4,4,32,64], w3 [3,3,64,128] -> [N,Ho3,Wo3,128], bitwise
+// cf32_frames_f32 + three cf32_conv_fwd(relu_out=True).  Raises on a shape
+// cf32_shallow_form declines.
+at::Tensor shallow_fwd(at::Tensor x, at::Tensor w1, at::Tensor b1, at::Tensor w2, at::Tensor b2,
+                       at::Tensor w3, at::Tensor b3) {
+  check_nhwc(x, "frames");
+  TORCH_CHECK(x.scalar_type() == at::kByte, "cf32_shallow_fwd: frames must be uint8 NHWC");
+  const int64_t N = x.size(0), H = x.size(1), W = x.size(2), C = x.size(3);
+  const int64_t dims[3][4] = {{8, C, 32, 0}, {4, 32, 64, 0}, {3, 64, 128, 0}};
+  const at::Tensor* ws[3] = {&w1, &w2, &w3};
+  const at::Tensor* bs[3] = {&b1, &b2, &b3};
+  for (int i = 0; i < 3; ++i) {
+    check_w(*ws[i]);
+    TORCH_CHECK(ws[i]->size(0) == dims[i][0] && ws[i]->size(2) == dims[i][1] &&
+                    ws[i]->size(3) == dims[i][2],
+                "cf32_shallow_fwd: layer ", i + 1, " weights must be HWIO [", dims[i][0], ",",
+                dims[i][0], ",", dims[i][1], ",", dims[i][2], "]");
+    TORCH_CHECK(bs[i]->is_cuda() && bs[i]->scalar_type() == at::kFloat &&
+                    bs[i]->is_contiguous() && bs[i]->numel() == dims[i][2], "bias");
+  }
+  TORCH_CHECK(N <= INT_MAX && H <= INT_MAX && W <= INT_MAX &&
+                  sa::cf32::shallow_form(static_cast<int>(N), static_cast<int>(H),
+                                         static_cast<int>(W), static_cast<int>(C)),
+              "cf32_shallow_fwd: no kernel for ", N, " frames of ", H, "x", W, "x", C);
+  const c10::DeviceGuard g(x.device());
+  const int H1 = (H + 3) / 4, W1 = (W + 3) / 4, H2 = (H1 + 1) / 2, W2 = (W1 + 1) / 2;
+  auto y = at::empty({N, (H2 + 1) / 2, (W2 + 1) / 2, 128}, x.options().dtype(at::kFloat));
+  TORCH_CHECK(sa::cf32::shallow_fwd_launch(
+                  x.data_ptr<uint8_t>(), w1.data_ptr<float>(), b1.data_ptr<float>(),
+                  w2.data_ptr<float>(), b2.data_ptr<float>(), w3.data_ptr<float>(),
+                  b3.data_ptr<float>(), y.data_ptr<float>(), static_cast<int>(N),
+                  static_cast<int>(H), static_cast<int>(W), static_cast<int>(C), stream()),
+              "cf32_shallow_fwd: frames must be 4-byte aligned");
+  check_launch("cf32_shallow_fwd");
+  return y;
+}
+
 void relu_mask_(at::Tensor dy, at::Tensor ref) {
   TORCH_CHECK(dy.is_cuda() && dy.is_contiguous() && dy.scalar_type() == at::kFloat, "dy");
   TORCH_CHECK(ref.is_contiguous() && ref.scalar_type() == at::kFloat &&
@@ -633,6 +672,12 @@ void register_conv_f32_ops(pybind11::module& m) {
   // output rows per workgroup of cf32_res_block_fwd for a C-channel map of
   // width W (0: no instance); tests cross every band seam with it
   m.def("cf32_res_block_band", [](int C, int W) { return sa::cf32::wino_res_block_band(C, W); });
+  m.def("cf32_shallow_fwd", &shallow_fwd, arg("frames"), arg("w1"), arg("b1"), arg("w2"),
+        arg("b2"), arg("w3"), arg("b3"));
+  // 1 where cf32_shallow_fwd takes N uint8 frames of [H, W, C], else 0: the
+  // launcher's own decision, host arithmetic only
+  m.def("cf32_shallow_form",
+        [](int N, int H, int W, int C) { return sa::cf32::shallow_form(N, H, W, C); });
   m.def("cf32_maxpool_fwd", &maxpool_fwd);
   m.def("cf32_maxpool_bwd", &maxpool_bwd);
   m.def("cf32_relu_mask_", &relu_mask_);

@@ -129,7 +129,8 @@ int conv_cus();
 int conv_grid_cap(int n);
 // Test hook: the last launch of a direct kernel on this host thread.
 // family: conv_fwd, conv_pool_fwd, conv_wgrad, pool_wgrad, maxpool_bwd_blk,
-// maxpool_bwd, frames_tile, frames, or none (nothing since the last reset:
+// maxpool_bwd, frames_tile, frames, shallow_whole (ntiles = images, rows 0),
+// or none (nothing since the last reset:
 // the Winograd launchers took the calls).  rows = R (output / pooled rows per
 // tile); ntiles, rows and tiles_per_img are 0 for the non-persistent kernels.
 struct LaunchInfo {
@@ -282,6 +283,23 @@ bool maxpool_fwd_launch(const float* x, float* y, uint8_t* arg, int N, int H,
 bool maxpool_bwd_launch(const float* dy, const uint8_t* arg, float* dx, int N,
                         int H, int W, int C, int Hp, int Wp, int pb_h, int pb_w,
                         hipStream_t s);
+// The whole shallow conv torso for actor inference in one launch, one
+// workgroup per image (conv_f32.hip shallow_torso_kernel): uint8 frames
+// [N,H,W,C] (C 1..4) -> relu(conv3x3/2(relu(conv4x4/2(relu(conv8x8/4(x/255)
+// + b1)) + b2)) + b3) [N,Ho3,Wo3,128], every conv TF-SAME.  The frame, the
+// x / 255 table and both inner maps live in LDS only; w1 is the UNPADDED
+// HWIO [8,8,C,32], w2 [4,4,32,64], w3 [3,3,64,128], streamed through LDS.
+// Bitwise frames_f32_launch + three conv_launch calls (relu_out) on the
+// 4-channel image.  False (nothing launched) where shallow_form declines or a
+// pointer is not 4-byte aligned.  Reports family shallow_whole (grid_x
+// workgroups, ntiles = N) to conv_launch_info; the grid follows conv_grid_cap.
+bool shallow_fwd_launch(const uint8_t* frames, const float* w1, const float* b1,
+                        const float* w2, const float* b2, const float* w3, const float* b3,
+                        float* out, int N, int H, int W, int C, hipStream_t s);
+// 1 where shallow_fwd_launch takes N x [H, W, C] uint8 frames (72x96, 84x84
+// and 72x128 frames, C 1..4, 1 <= N <= kResBlockMaxFrames, and the LDS plan
+// fits), else 0.  Host arithmetic only.
+int shallow_form(int N, int H, int W, int C);
 // uint8 frames [P pixels][Cs <= 4] -> fp32 [P][4] (x / 255, zero-padded)
 void frames_f32_launch(const uint8_t* x, float* y, int64_t P, int Cs, hipStream_t s);
 // dy *= (ref > 0), fp32, n % 4 == 0

@@ -519,6 +519,207 @@ __global__ __launch_bounds__(kThreads, 2) void conv_fwd_kernel(ConvArgs a, int R
   }
 }
 
+// ------------------------------------------------- whole shallow torso
+// Actor inference: the three convs of the shallow torso (8x8/4, 4x4/2, 3x3/2,
+// TF-SAME, bias + ReLU each) in one kernel, one workgroup per image.  LDS
+// (floats):
+//   lut [256]            the exact x / 255 table (frames_f32_kernel's)
+//   zero [kShZero]       a zero pixel: out-of-image taps read it
+//   wbuf [2][kShChunk]   weight chunks of layers 1 and 2, double-buffered
+//   a1 [H1*W1][40]       layer-1 output; dead in layer 3, which streams its
+//                        larger weight chunks through it
+//   a2 [H2*W2][72]       layer-2 output; before that the uint8 frame
+// Per output element the MFMA sequence is conv_fwd_kernel's: zero
+// accumulator, taps (ky, kx) in order, 16-channel blocks b, then v within
+// VPL, channel 16 b + VPL g + v in k slot g on both operands (layer 1: the
+// 4-channel image, k slot = channel, pad channels 0 on both operands), bias
+// after the last MFMA, then ReLU - so the features are bitwise those of
+// frames_f32 + three conv_fwd launches.  Out-of-image taps multiply the
+// weight by 0.f exactly as the zero-padded LDS image of conv_fwd_kernel.
+//
+// Weights stream from global memory (L2-resident across workgroups) in
+// chunks of SPC (tap, block) steps laid out as MFMA A fragments
+// [step][g][co][VPL]: the next chunk is loaded into registers before the
+// current chunk's MFMAs and committed to the other buffer after them, one
+// barrier per chunk.  Waves split the 16-channel output blocks (HW classes,
+// HPW blocks each) and / or the 16-pixel groups (WG classes, <= MAXG groups
+// each); accumulators stay in registers across the chunks of a layer.
+constexpr int kShZero = 128;
+constexpr int kShChunk = 2048;      // floats per weight chunk, layers 1 and 2
+constexpr int kShChunk3 = 8192;     // layer 3: one tap (64 x 128)
+constexpr int kShG1 = 9, kShG2 = 9, kShG3 = 3;  // 16-pixel groups per wave
+
+struct ShallowArgs {
+  const uint8_t* frames;  // [N, H, W, C]
+  const float *w1, *b1, *w2, *b2, *w3, *b3;
+  float* out;             // [N, H3, W3, 128]
+  int N, H, W, C;
+  int H1, W1, pt1, pl1;   // layer outputs and TF-SAME pad_before
+  int H2, W2, pt2, pl2;
+  int H3, W3, pt3, pl3;
+};
+
+// One layer over the LDS input x_s ([Hi*Wi][fwd_pitch(CINP)] floats, or the
+// uint8 frame [Hi*Wi][Ci] when U8) -> out [Ho*Wo][opitch] (LDS or global).
+// Ends with a barrier: the output is visible and wbuf / x_s are free.
+template <int K, int S, int CINP, int COUT, int SPC, int HPW, int WG, int MAXG, bool U8>
+__device__ __forceinline__ void shallow_layer(const float* __restrict__ w, int wcin,
+                                              const float* __restrict__ bias,
+                                              const void* x_s, const float* lut,
+                                              const float* zero, int Hi, int Wi, int Ci,
+                                              int pt, int pl, int Ho, int Wo, float* wbuf,
+                                              float* out, int opitch) {
+  constexpr int PP = fwd_pitch(CINP);
+  constexpr int VPL = CINP >= 16 ? 4 : 1;
+  constexpr int NB = CINP >= 16 ? CINP / 16 : 1;
+  constexpr int STEPS = K * K * NB;
+  constexpr int NCH = STEPS / SPC;
+  constexpr int CHF = SPC * 4 * VPL * COUT;  // floats per chunk
+  constexpr int UPT = CHF / VPL / kThreads;  // VPL-float units per thread
+  constexpr int HW = 4 / WG;
+  static_assert(CINP == 4 || CINP % 16 == 0, "CINP");
+  static_assert(STEPS % SPC == 0 && (CHF / VPL) % kThreads == 0, "chunking");
+  static_assert(HW * HPW * 16 == COUT, "wave split");
+  static_assert(U8 == (CINP == 4), "the frame is the 4-channel layer");
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int g = lane >> 4, c16 = lane & 15;
+  const int hsel = wave % HW, gsel = wave / HW;
+  const int P = Ho * Wo;
+  const int ngroups = (P + 15) >> 4;
+
+  float pre[UPT][VPL];
+  auto wload = [&](int c) {
+#pragma unroll
+    for (int k = 0; k < UPT; ++k) {
+      const int u = threadIdx.x + k * kThreads;
+      const int co = u % COUT, q = u / COUT;
+      const int st = c * SPC + (q >> 2), gq = q & 3;
+      if constexpr (VPL == 4) {
+        const int tap = st / NB, b = st - (st / NB) * NB;
+        const float* p = w + ((tap * CINP + 16 * b + 4 * gq) * COUT + co);
+#pragma unroll
+        for (int v = 0; v < 4; ++v) pre[k][v] = p[v * COUT];
+      } else {
+        pre[k][0] = gq < wcin ? w[(st * wcin + gq) * COUT + co] : 0.f;
+      }
+    }
+  };
+  auto wcommit = [&](float* buf) {
+#pragma unroll
+    for (int k = 0; k < UPT; ++k) {
+      const int u = threadIdx.x + k * kThreads;
+      if constexpr (VPL == 4)
+        *reinterpret_cast<f4*>(buf + 4 * u) = f4{pre[k][0], pre[k][1], pre[k][2], pre[k][3]};
+      else
+        buf[u] = pre[k][0];
+    }
+  };
+
+  // this wave's pixel groups gsel + WG j: top-left source position per lane
+  int iy0[MAXG], ix0[MAXG];
+  f4 acc[MAXG][HPW];
+#pragma unroll
+  for (int j = 0; j < MAXG; ++j) {
+    const int p = (gsel + WG * j) * 16 + c16;
+    const int pp = p < P ? p : 0;
+    const int oy = pp / Wo, ox = pp - oy * Wo;
+    iy0[j] = oy * S - pt;
+    ix0[j] = ox * S - pl;
+#pragma unroll
+    for (int i = 0; i < HPW; ++i) acc[j][i] = f4{0.f, 0.f, 0.f, 0.f};
+  }
+
+  wload(0);
+  wcommit(wbuf);
+  __syncthreads();  // chunk 0 (and, before layer 1, the staged frame) visible
+  for (int c = 0; c < NCH; ++c) {
+    const float* wcur = wbuf + (c & 1) * CHF;
+    if (c + 1 < NCH) wload(c + 1);  // in flight during the MFMAs below
+    // long chunks (layer 1: 16 taps) stay rolled: unrolled, the operand reads
+    // of every tap are hoisted and the kernel spills
+#pragma unroll(SPC <= 4 ? SPC : 1)
+    for (int sl = 0; sl < SPC; ++sl) {
+      const int st = c * SPC + sl;
+      const int tap = st / NB, b = st - (st / NB) * NB;
+      const int ky = tap / K, kx = tap - (tap / K) * K;
+      float av[HPW][VPL], bv[MAXG][VPL];
+#pragma unroll
+      for (int i = 0; i < HPW; ++i)
+        lds_get<VPL>(wcur + ((sl * 4 + g) * COUT + 16 * (hsel + HW * i) + c16) * VPL, av[i]);
+#pragma unroll
+      for (int j = 0; j < MAXG; ++j) {
+        const int iy = iy0[j] + ky, ix = ix0[j] + kx;
+        const bool ok = static_cast<unsigned>(iy) < static_cast<unsigned>(Hi) &&
+                        static_cast<unsigned>(ix) < static_cast<unsigned>(Wi);
+        if constexpr (U8) {
+          const bool okc = ok && g < Ci;
+          const int at = okc ? (iy * Wi + ix) * Ci + g : 0;
+          const float t = lut[static_cast<const uint8_t*>(x_s)[at]];
+          bv[j][0] = okc ? t : 0.f;
+        } else {
+          const float* p = ok ? static_cast<const float*>(x_s) + (iy * Wi + ix) * PP : zero;
+          lds_get<VPL>(p + 16 * b + VPL * g, bv[j]);
+        }
+      }
+      __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+      for (int v = 0; v < VPL; ++v)
+#pragma unroll
+        for (int j = 0; j < MAXG; ++j) {
+          if (gsel + WG * j >= ngroups) continue;  // wave-uniform
+#pragma unroll
+          for (int i = 0; i < HPW; ++i) acc[j][i] = mfma4(av[i][v], bv[j][v], acc[j][i]);
+        }
+    }
+    if (c + 1 < NCH) {
+      wcommit(wbuf + ((c + 1) & 1) * CHF);
+    } else {
+#pragma unroll
+      for (int j = 0; j < MAXG; ++j) {
+        const int p = (gsel + WG * j) * 16 + c16;
+        if (p >= P) continue;
+#pragma unroll
+        for (int i = 0; i < HPW; ++i) {
+          const int co = 16 * (hsel + HW * i) + 4 * g;
+          f4 v = acc[j][i];
+#pragma unroll
+          for (int r = 0; r < 4; ++r) v[r] = fmaxf(v[r] + bias[co + r], 0.f);
+          *reinterpret_cast<f4*>(out + p * opitch + co) = v;
+        }
+      }
+    }
+    __syncthreads();  // every wave is done with chunk c; chunk c + 1 visible
+  }
+}
+
+__global__ __launch_bounds__(kThreads) void shallow_torso_kernel(ShallowArgs a) {
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  float* lut = smem;
+  float* zero = lut + 256;
+  float* wbuf = zero + kShZero;
+  float* a1 = wbuf + 2 * kShChunk;
+  float* a2 = a1 + a.H1 * a.W1 * fwd_pitch(32);
+  lut[threadIdx.x] = static_cast<float>(static_cast<double>(threadIdx.x) / 255.0);
+  if (threadIdx.x < kShZero) zero[threadIdx.x] = 0.f;
+  const int ndw = (a.H * a.W * a.C) >> 2;  // whole dwords (shallow_form)
+  for (int n = blockIdx.x; n < a.N; n += gridDim.x) {
+    // the previous image's layer 3 ended with a barrier: a2 is free
+    const uint32_t* src =
+        reinterpret_cast<const uint32_t*>(a.frames + static_cast<int64_t>(n) * ndw * 4);
+    uint32_t* fr = reinterpret_cast<uint32_t*>(a2);
+    for (int d = threadIdx.x; d < ndw; d += kThreads) fr[d] = src[d];
+    shallow_layer<8, 4, 4, 32, 16, 2, 4, kShG1, true>(
+        a.w1, a.C, a.b1, a2, lut, zero, a.H, a.W, a.C, a.pt1, a.pl1, a.H1, a.W1, wbuf, a1,
+        fwd_pitch(32));
+    shallow_layer<4, 2, 32, 64, 2, 1, 1, kShG2, false>(
+        a.w2, 32, a.b2, a1, lut, zero, a.H1, a.W1, 0, a.pt2, a.pl2, a.H2, a.W2, wbuf, a2,
+        fwd_pitch(64));
+    shallow_layer<3, 2, 64, 128, 4, 2, 1, kShG3, false>(
+        a.w3, 64, a.b3, a2, lut, zero, a.H2, a.W2, 0, a.pt3, a.pl3, a.H3, a.W3, a1,
+        a.out + static_cast<int64_t>(n) * a.H3 * a.W3 * 128, 128);
+  }
+}
+
 // ------------------------------------------------------- fused conv + pool
 // Stage head of the deep torso: conv3x3/1 SAME + bias, then the 3x3/2 SAME
 // max-pool, in one persistent kernel.  A tile is R pooled rows of one image:
@@ -1842,6 +2043,62 @@ bool maxpool_bwd_launch(const float* dy, const uint8_t* arg, float* dx, int N, i
   note_launch("maxpool_bwd", static_cast<int>(grid.x), static_cast<int>(grid.y), 0, 0, 0);
   hipLaunchKernelGGL(maxpool_bwd_kernel, grid, dim3(256), 0, s, dy, arg, dx, N, H, W, C, Hp,
                      Wp, pb_h, pb_w, sh);
+  return true;
+}
+
+namespace {
+// TF-SAME geometry of one conv: output size and pad_before
+void same_geom(int n, int k, int s, int* out, int* before) {
+  *out = (n + s - 1) / s;
+  *before = std::max((*out - 1) * s + k - n, 0) / 2;
+}
+
+// Geometry and LDS bytes of the whole shallow torso on [H, W, C] frames;
+// 0 where the plan does not fit the kernel's buffers and wave split.
+size_t shallow_plan(int H, int W, int C, ShallowArgs* a) {
+  a->H = H; a->W = W; a->C = C;
+  same_geom(H, 8, 4, &a->H1, &a->pt1);
+  same_geom(W, 8, 4, &a->W1, &a->pl1);
+  same_geom(a->H1, 4, 2, &a->H2, &a->pt2);
+  same_geom(a->W1, 4, 2, &a->W2, &a->pl2);
+  same_geom(a->H2, 3, 2, &a->H3, &a->pt3);
+  same_geom(a->W2, 3, 2, &a->W3, &a->pl3);
+  const size_t f1 = static_cast<size_t>(a->H1) * a->W1 * fwd_pitch(32);
+  const size_t f2 = static_cast<size_t>(a->H2) * a->W2 * fwd_pitch(64);
+  const size_t bytes = 4 * (256 + kShZero + 2 * kShChunk + f1 + f2);
+  const size_t frame = static_cast<size_t>(H) * W * C;
+  if (frame % 4 != 0 || frame > 4 * f2) return 0;  // dword rows, staged in a2
+  if (f1 < 2 * static_cast<size_t>(kShChunk3)) return 0;  // layer 3 streams through a1
+  if ((a->H1 * a->W1 + 15) / 16 > 4 * kShG1 || (a->H2 * a->W2 + 15) / 16 > kShG2 ||
+      (a->H3 * a->W3 + 15) / 16 > kShG3)
+    return 0;
+  return bytes <= kLdsHard ? bytes : 0;
+}
+}  // namespace
+
+int shallow_form(int N, int H, int W, int C) {
+  if (N < 1 || N > kResBlockMaxFrames || C < 1 || C > 4) return 0;
+  if (!((H == 72 && W == 96) || (H == 84 && W == 84) || (H == 72 && W == 128))) return 0;
+  ShallowArgs a{};
+  return shallow_plan(H, W, C, &a) > 0 ? 1 : 0;
+}
+
+bool shallow_fwd_launch(const uint8_t* frames, const float* w1, const float* b1,
+                        const float* w2, const float* b2, const float* w3, const float* b3,
+                        float* out, int N, int H, int W, int C, hipStream_t s) {
+  if (!shallow_form(N, H, W, C)) return false;
+  if ((reinterpret_cast<uintptr_t>(frames) & 3) != 0 || (reinterpret_cast<uintptr_t>(out) & 15) != 0)
+    return false;
+  ShallowArgs a{};
+  const size_t lds = shallow_plan(H, W, C, &a);
+  a.frames = frames;
+  a.w1 = w1; a.b1 = b1; a.w2 = w2; a.b2 = b2; a.w3 = w3; a.b3 = b3;
+  a.out = out;
+  a.N = N;
+  const int G = capped(std::min(N, conv_cus()));
+  allow_lds(shallow_torso_kernel, lds);
+  note_launch("shallow_whole", G, 1, N, 0, 1);
+  hipLaunchKernelGGL(shallow_torso_kernel, dim3(G), dim3(kThreads), lds, s, a);
   return true;
 }
 

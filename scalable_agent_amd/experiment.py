@@ -162,6 +162,29 @@ def _log_torso_blocks(flags, model):
   asked = getattr(flags, 'torso_blocks', 'ops')
   used = model.torso_blocks
   agent = model.agent
+  if asked == 'whole':
+    hip = (getattr(agent, 'backend', 'torch') == 'hip' and
+           model.device.type == 'cuda')
+    frame = 'x'.join(str(d) for d in agent.frame_shape)
+    if used == 'whole':
+      log.info('actor inference torso blocks: whole (x / 255 and the three '
+               'convs of the shallow torso in one launch on %s frames)', frame)
+      return
+    if agent.torso_kind == 'deep' and used != 'ops':
+      log.info('actor inference torso blocks: %s (--torso_blocks=whole on a '
+               'deep torso runs as heads)', used)
+      return
+    if not hip:
+      why = 'the torch backend has no torso kernel'
+    elif str(agent.compute_dtype) != 'torch.float32':
+      why = 'the one-launch torso is fp32 only'
+    elif agent.torso_kind == 'deep':
+      why = 'bf16 inference already runs one kernel per block'
+    else:
+      why = 'the kernel does not take %s frames' % frame
+    log.info('actor inference torso blocks: %s (--torso_blocks=whole does not '
+             'apply: %s)', used, why)
+    return
   if asked == used == 'stage':
     form = agent.torso_stage_form(model.device.type == 'cuda')
     log.info('actor inference torso blocks: stage (%s in one launch)',

@@ -117,9 +117,10 @@ def build_parser() -> argparse.ArgumentParser:
                       'more the actors sample with torch.multinomial).  bf16 '
                       'inference runs ops.')
   p.add_argument('--torso_blocks', default='ops',
-                 choices=['ops', 'fused', 'stage', 'heads'],
-                 help='Residual blocks of the fp32 HIP deep torso in actor '
-                      'inference (no autograd, at most 512 frames per launch): '
+                 choices=['ops', 'fused', 'stage', 'heads', 'whole'],
+                 help='Fused forms of the fp32 HIP torso in actor '
+                      'inference (no autograd, at most 512 frames per launch).  '
+                      'Deep torso: '
                       'ops = two Winograd convs per block; fused = ONE kernel '
                       'per block; stage = as fused, and the last stage (its '
                       'head, max-pool and both blocks at an 18x24 input such '
@@ -129,10 +130,15 @@ def build_parser() -> argparse.ArgumentParser:
                       'stage-0 and stage-1 heads (conv, bias, max-pool) in ONE '
                       'kernel each, stage 0 straight from the uint8 frames '
                       '(72x96, 84x84 and 72x128 frames; other shapes run as '
-                      'stage).  All four give bitwise the same '
-                      'features.  bf16 inference fuses its blocks already; '
-                      'the shallow torso and the torch backend have nothing '
-                      'to fuse and run as with ops.')
+                      'stage).  Shallow torso: whole = x / 255 and the three '
+                      'convs in ONE kernel, one workgroup per frame, every '
+                      'intermediate in LDS (72x96, 84x84 and 72x128 frames '
+                      'with 1-4 channels; other shapes run as ops); fused, '
+                      'stage and heads have nothing to fuse there and run as '
+                      'ops.  whole on a deep torso means heads.  All forms '
+                      'give bitwise the same features.  bf16 inference fuses '
+                      'its blocks already, and bf16 and the torch backend run '
+                      'as with ops.')
   p.add_argument('--inference_device', default='auto',
                  help='Device of the actor-inference model: auto = the '
                       'learner device; e.g. cuda:1 or cpu.')

@@ -141,8 +141,14 @@ class InferenceModel(object):
     blocks, in one kernel and every other residual block as one kernel:
     Agent(torso_blocks='stage') where the stage kernel takes the frames),
     'fused' (one kernel per residual block: 'fused', or 'stage' on frames the
-    stage kernel does not take), else 'ops'."""
+    stage kernel does not take), else 'ops'.  'whole': the shallow torso's
+    x / 255 and three convs as one kernel (Agent(torso_blocks='whole') on an
+    fp32 HIP shallow agent whose frames the kernel takes); a deep agent built
+    with 'whole' reports what 'heads' would."""
     cuda = self.device.type == 'cuda'
+    whole = getattr(self.agent, 'torso_whole_form', None)
+    if whole is not None and whole(cuda):
+      return 'whole'
     fused = getattr(self.agent, 'torso_blocks_fused', None)
     if fused is None or not fused(cuda):
       return 'ops'

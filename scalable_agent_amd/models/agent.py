@@ -132,8 +132,10 @@ class Agent(nn.Module):
     # launch where its whole map fits a workgroup (_DeepTorsoF32Stage);
     # 'heads': the same, and the stage-0 and stage-1 heads in one launch each
     # straight from the uint8 frames (_DeepTorsoF32Heads); 'ops': two
-    # Winograd convs per block
-    if torso_blocks not in ('ops', 'fused', 'stage', 'heads'):
+    # Winograd convs per block.  'whole': a no-grad forward of the fp32 HIP
+    # SHALLOW torso runs x / 255 and its three convs as ONE kernel where it
+    # applies (torso_whole_form); on a deep torso it means 'heads'
+    if torso_blocks not in ('ops', 'fused', 'stage', 'heads', 'whole'):
       raise ValueError('unknown torso_blocks %r' % (torso_blocks,))
     self.torso_blocks = torso_blocks
     # 'fused': the T = 1 inference step after the torso-FC GEMM is ONE kernel
@@ -535,11 +537,13 @@ class Agent(nn.Module):
             isinstance(generator, PhiloxStream))
 
   def torso_blocks_fused(self, cuda=True):
-    """True when `torso_blocks='fused'`, `'stage'` or `'heads'` is honoured for a no-grad
+    """True when `torso_blocks='fused'`, `'stage'` or `'heads'` (or `'whole'`,
+    which means 'heads' on a deep torso) is honoured for a no-grad
     forward of CUDA frames: HIP backend, deep torso, and the exact-fp32 torso
     kernels run it (the bf16 torso fuses its blocks on its own; the shallow
-    torso has none).  Otherwise the torso runs as with 'ops'."""
-    return (self.torso_blocks in ('fused', 'stage', 'heads') and
+    torso has none: see torso_whole_form).  Otherwise the torso runs as with
+    'ops'."""
+    return (self.torso_blocks in ('fused', 'stage', 'heads', 'whole') and
             self.backend == 'hip' and cuda and self.torso_kind == 'deep' and
             not _bf16_torso_ready(self))
 
@@ -549,7 +553,7 @@ class Agent(nn.Module):
     blocks in one launch), 'tail' (both blocks in one launch), or None: not
     asked for, or the torso runs as 'fused' / 'ops' there
     (torso_blocks_fused)."""
-    if (self.torso_blocks not in ('stage', 'heads') or
+    if (self.torso_blocks not in ('stage', 'heads', 'whole') or
         not self.torso_blocks_fused(cuda)):
       return None
     from ..ops import conv_f32
@@ -559,10 +563,26 @@ class Agent(nn.Module):
     """Which of the stage-0 / stage-1 heads `torso_blocks='heads'` runs as one
     launch each on this agent's frames: a tuple of stage numbers, empty where
     both decline; None: not asked for, or the torso runs as 'ops' there."""
-    if self.torso_blocks != 'heads' or not self.torso_blocks_fused(cuda):
+    if (self.torso_blocks not in ('heads', 'whole') or
+        not self.torso_blocks_fused(cuda)):
       return None
     from ..ops import conv_f32
     return conv_f32.head_form(self.frame_shape)
+
+  def torso_whole_form(self, cuda=True):
+    """What `torso_blocks='whole'` runs for a no-grad forward of CUDA frames
+    of this agent's shape: 'shallow' (x / 255 and the three convs of the
+    shallow torso in one launch: fp32 HIP agent, a frame the kernel takes),
+    or None: not asked for, a deep torso (which runs as 'heads'), or the
+    torso runs as 'ops' there."""
+    if (self.torso_blocks != 'whole' or self.backend != 'hip' or not cuda or
+        self.torso_kind != 'shallow' or
+        self.compute_dtype != torch.float32):
+      return None
+    from ..ops import conv_f32
+    if not conv_f32.supports(self):
+      return None
+    return conv_f32.whole_form(self.frame_shape)
 
   def _fused_step(self, actions, env_outputs, core_state, generator, epilogue):
     """The T = 1 actor step with the fused core: torso, the torso-FC GEMM

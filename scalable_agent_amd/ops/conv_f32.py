@@ -220,6 +220,15 @@ def stage_form(frame_shape, frames=1):
   return {2: 'stage', 1: 'tail'}.get(ext().cf32_stage_form(frames, h, w, 32))
 
 
+def whole_form(frame_shape, frames=1):
+  """What torso_blocks='whole' runs for the shallow torso on `frames` frames
+  of this shape: 'shallow' (cf32_shallow_fwd: x / 255 and the three convs in
+  one launch) or None (the launches of 'ops').  The launcher's own decision
+  (cf32_shallow_form), host arithmetic only."""
+  h, w, c = frame_shape[0], frame_shape[1], frame_shape[2]
+  return 'shallow' if ext().cf32_shallow_form(frames, h, w, c) else None
+
+
 def _deep_forward(ctx, frames, params, stage=False, heads=False):
   """Forward of the deep torso.  ctx None (_DeepTorsoF32Infer): residual
   blocks run cf32_res_block_fwd (both convs in one launch, t only in LDS,
@@ -423,8 +432,20 @@ def torso_forward_f32(agent, frames):
   if frames.dtype != torch.uint8:
     raise TypeError('HIP torso expects uint8 frames, got %s' % frames.dtype)
   frames = frames.contiguous()
+  from .conv import FUSED_BLOCK_MAX_FRAMES
+  blocks = getattr(agent, 'torso_blocks', 'ops')
   if agent.torso_kind == 'shallow':
-    return _chunked(_ShallowTorsoF32, frames, shallow_param_list(agent))
+    params = shallow_param_list(agent)
+    # actor inference of an fp32 agent built with torso_blocks='whole': the
+    # whole conv torso in one launch (w1 unpadded, no fp32 image), bitwise
+    # the launches below; the learner and any call under autograd take those
+    if (blocks == 'whole' and not torch.is_grad_enabled() and
+        agent.compute_dtype == torch.float32 and
+        frames.shape[0] <= FUSED_BLOCK_MAX_FRAMES and
+        whole_form(frames.shape[1:], frames.shape[0])):
+      x = ext().cf32_shallow_fwd(frames, *params)
+      return x.reshape(x.shape[0], -1)
+    return _chunked(_ShallowTorsoF32, frames, params)
   from .conv import deep_param_list
   params = deep_param_list(agent)
   cache = getattr(agent, '_inference_cache', None)
@@ -433,16 +454,16 @@ def torso_forward_f32(agent, frames):
     # an inference agent's stage-0 weights, zero-padded to the image's 4
     # channels once per weight publish (no concatenation kernel per step)
     params = [cache['w0pad']] + params[1:]
-  from .conv import FUSED_BLOCK_MAX_FRAMES
   # actor inference (no autograd, a board's worth of frames) of an agent
   # built with torso_blocks='fused': one launch per residual block; 'stage':
-  # and one for the last stage; 'heads': and one per stage-0 / stage-1 head
-  blocks = getattr(agent, 'torso_blocks', 'ops')
+  # and one for the last stage; 'heads' (and 'whole', which means 'heads' on
+  # the deep torso): and one per stage-0 / stage-1 head
   fn = _DeepTorsoF32
-  if (blocks in ('fused', 'stage', 'heads') and not torch.is_grad_enabled() and
+  if (blocks in ('fused', 'stage', 'heads', 'whole') and
+      not torch.is_grad_enabled() and
       frames.shape[0] <= FUSED_BLOCK_MAX_FRAMES):
-    fn = {'stage': _DeepTorsoF32Stage,
-          'heads': _DeepTorsoF32Heads}.get(blocks, _DeepTorsoF32Infer)
+    fn = {'stage': _DeepTorsoF32Stage, 'heads': _DeepTorsoF32Heads,
+          'whole': _DeepTorsoF32Heads}.get(blocks, _DeepTorsoF32Infer)
   return _chunked(fn, frames, params)
 
 
