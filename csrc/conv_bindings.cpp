@@ -3,6 +3,8 @@
 #include <c10/hip/HIPStream.h>
 #include <c10/core/DeviceGuard.h>
 
+#include <climits>
+
 #include "kernels/conv_launchers.h"
 
 namespace {
@@ -192,6 +194,72 @@ void conv1_pool_bwd(at::Tensor dP, at::Tensor arg, at::Tensor x, at::Tensor dw,
                                   x.size(2), C, pb_h, pb_w, stream(), ptr_or_null(part));
 }
 
+// ---- the shallow torso on bf16 MFMA (kernels/conv_shallow_bf16.hip) ----
+constexpr int64_t kSbSteps[3] = {8, 16, 18};    // K = 32 steps per layer
+constexpr int64_t kSbCout[3] = {32, 64, 128};
+
+// fp32 HWIO w1 [8,8,C<=4,32], w2 [4,4,32,64], w3 [3,3,64,128] -> the kernel's
+// bf16 B-operand layout [kstep][ntile][lane][8] (w1 zero-padded to 4 input
+// channels; one RNE rounding).  Off the hot path: once per weight publish.
+std::vector<at::Tensor> shallow_bf16_pack(at::Tensor w1, at::Tensor w2, at::Tensor w3) {
+  const at::Tensor* ws[3] = {&w1, &w2, &w3};
+  const int64_t dims[3][2] = {{8, -1}, {4, 32}, {3, 64}};
+  std::vector<at::Tensor> out;
+  for (int i = 0; i < 3; ++i) {
+    const at::Tensor& w = *ws[i];
+    TORCH_CHECK(w.dim() == 4 && w.scalar_type() == at::kFloat && w.size(0) == dims[i][0] &&
+                    w.size(1) == dims[i][0] && w.size(3) == kSbCout[i] &&
+                    (i == 0 ? (w.size(2) >= 1 && w.size(2) <= 4) : w.size(2) == dims[i][1]),
+                "shallow_bf16_pack: layer ", i + 1, " weights must be fp32 HWIO [", dims[i][0],
+                ",", dims[i][0], ",", (i == 0 ? "C<=4" : (i == 1 ? "32" : "64")), ",",
+                kSbCout[i], "]");
+    at::Tensor f = w.detach();
+    if (i == 0 && f.size(2) != 4) f = at::constant_pad_nd(f, {0, 0, 0, 4 - f.size(2)}, 0);
+    // [K, cout] -> (kstep, g, j, ntile, m) -> (kstep, ntile, g, m, j); lane = 16 g + m
+    f = f.reshape({kSbSteps[i], 4, 8, kSbCout[i] / 16, 16}).permute({0, 3, 1, 4, 2});
+    out.push_back(f.to(at::kBFloat16).contiguous().reshape({-1}));
+  }
+  return out;
+}
+
+at::Tensor shallow_bf16_fwd(at::Tensor x, at::Tensor w1p, at::Tensor b1, at::Tensor w2p,
+                            at::Tensor b2, at::Tensor w3p, at::Tensor b3) {
+  TORCH_CHECK(x.is_cuda() && x.is_contiguous() && x.dim() == 4,
+              "shallow_bf16_fwd: frames must be a contiguous NHWC GPU tensor");
+  TORCH_CHECK(x.scalar_type() == at::kByte, "shallow_bf16_fwd: frames must be uint8 NHWC");
+  const int64_t N = x.size(0), H = x.size(1), W = x.size(2), C = x.size(3);
+  const at::Tensor* ws[3] = {&w1p, &w2p, &w3p};
+  const at::Tensor* bs[3] = {&b1, &b2, &b3};
+  for (int i = 0; i < 3; ++i) {
+    const int64_t want = kSbSteps[i] * 32 * kSbCout[i];
+    TORCH_CHECK(ws[i]->is_cuda() && ws[i]->is_contiguous() &&
+                    ws[i]->scalar_type() == at::kBFloat16 && ws[i]->numel() == want,
+                "shallow_bf16_fwd: layer ", i + 1, " packed weights must be ", want,
+                " contiguous bf16 on the GPU (shallow_bf16_pack)");
+    TORCH_CHECK(reinterpret_cast<uintptr_t>(ws[i]->data_ptr()) % 16 == 0,
+                "shallow_bf16_fwd: packed weights must be 16-byte aligned");
+    TORCH_CHECK(bs[i]->is_cuda() && bs[i]->scalar_type() == at::kFloat &&
+                    bs[i]->is_contiguous() && bs[i]->numel() == kSbCout[i],
+                "shallow_bf16_fwd: layer ", i + 1, " bias must be fp32 [", kSbCout[i], "]");
+  }
+  TORCH_CHECK(N <= INT_MAX && H <= INT_MAX && W <= INT_MAX && C <= INT_MAX &&
+                  sa::conv::shallow_bf16_form(static_cast<int>(N), static_cast<int>(H),
+                                              static_cast<int>(W), static_cast<int>(C)),
+              "shallow_bf16_fwd: no kernel for ", N, " frames of ", H, "x", W, "x", C);
+  const c10::DeviceGuard g(x.device());
+  const int64_t H1 = (H + 3) / 4, W1 = (W + 3) / 4, H2 = (H1 + 1) / 2, W2 = (W1 + 1) / 2;
+  auto y = at::empty({N, (H2 + 1) / 2, (W2 + 1) / 2, 128}, x.options().dtype(at::kBFloat16));
+  TORCH_CHECK(sa::conv::shallow_bf16_fwd_launch(
+                  x.data_ptr<uint8_t>(), w1p.data_ptr(), b1.data_ptr<float>(), w2p.data_ptr(),
+                  b2.data_ptr<float>(), w3p.data_ptr(), b3.data_ptr<float>(), y.data_ptr(),
+                  static_cast<int>(N), static_cast<int>(H), static_cast<int>(W),
+                  static_cast<int>(C), stream()),
+              "shallow_bf16_fwd: frames must be 4-byte aligned");
+  const hipError_t e = hipGetLastError();
+  TORCH_CHECK(e == hipSuccess, "shallow_bf16_fwd: launch failed: ", hipGetErrorString(e));
+  return y;
+}
+
 }  // namespace
 
 void register_conv_ops(pybind11::module& m) {
@@ -206,6 +274,13 @@ void register_conv_ops(pybind11::module& m) {
         pybind11::arg("db"), pybind11::arg("relu_act") = true);
   m.def("pool_conv_bwd", &pool_conv_bwd);
   m.def("conv1_pool_bwd", &conv1_pool_bwd);
+  m.def("shallow_bf16_fwd", &shallow_bf16_fwd, pybind11::arg("frames"), pybind11::arg("w1p"),
+        pybind11::arg("b1"), pybind11::arg("w2p"), pybind11::arg("b2"), pybind11::arg("w3p"),
+        pybind11::arg("b3"));
+  m.def("shallow_bf16_pack", &shallow_bf16_pack);
+  // 1 where shallow_bf16_fwd takes N uint8 frames of [H, W, C], else 0
+  m.def("shallow_bf16_form",
+        [](int N, int H, int W, int C) { return sa::conv::shallow_bf16_form(N, H, W, C); });
   // read-only record of a family's last launch ("" = the most recent one)
   m.def("conv_launch_info", [](const std::string& family) {
           const sa::conv::LaunchInfo i = sa::conv::launch_info(family.c_str());

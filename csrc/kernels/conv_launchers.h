@@ -47,6 +47,26 @@ void conv1_pool_bwd_launch(const void* dP, const uint8_t* argmax,
 // per-workgroup slots in a fixed order instead of with float atomics.
 int64_t wgrad_part_floats(int cin, int cout, bool conv1);
 
+// The whole shallow torso (8x8/4 -> 32, 4x4/2 -> 64, 3x3/2 -> 128, TF-SAME,
+// bias + ReLU each) of uint8 NHWC frames [N,H,W,C] in one launch on bf16 MFMA
+// (conv_shallow_bf16.hip): x / 255, the three convs, bf16 NHWC features
+// [N,H3,W3,128].  w1p/w2p/w3p: bf16 weights in the B-operand layout
+// [kstep][ntile][lane][8] (8 x 2 x 64 x 8, 16 x 4 x 64 x 8, 18 x 8 x 64 x 8
+// elements, 16-byte aligned); biases fp32.  False (nothing launched) where
+// shallow_bf16_form declines or a pointer is misaligned (frames 4, out 8
+// bytes).  Reports family "shallow_bf16" (grid, ntiles = N) to launch_info;
+// conv_tune("shallow_bf16_grid", g) caps the grid at g workgroups (0: none).
+bool shallow_bf16_fwd_launch(const uint8_t* frames, const void* w1p, const float* b1,
+                             const void* w2p, const float* b2, const void* w3p,
+                             const float* b3, void* out, int N, int H, int W, int C,
+                             hipStream_t s);
+// 1 where shallow_bf16_fwd_launch takes N x [H, W, C] uint8 frames (72x96,
+// 84x84 or 72x128 with C <= 4, 1 <= N <= 512), else 0.
+int shallow_bf16_form(int N, int H, int W, int C);
+// Between conv_shallow_bf16.hip and conv_torso.hip (grid cap, launch record).
+int shallow_bf16_grid_max();
+void shallow_bf16_note(int grid, int grid_max, int ntiles);
+
 // Read-only record of the last launch of a launcher family (host side; the
 // tests assert from it that the path they mean to test actually ran).
 struct LaunchInfo {

@@ -1684,6 +1684,7 @@ struct ConvTune {
   int specialize = 1;     // use compile-time-geometry kernels when they match
   int ablate = 0;         // timing-only, -DSA_CONV_ABLATE builds: skip phases
   int deterministic = 0;  // wgrad: per-workgroup slots + fixed-order reduce
+  int shallow_bf16_grid = 0;  // conv_shallow_bf16.hip: max workgroups (0 = no cap)
 };
 constexpr ConvTune kDef{};
 static ConvTune g_tune;
@@ -1697,7 +1698,8 @@ int conv_tune_set(const char* key, int value) {
       {"px_pool_bwd", &g_tune.px_pool_bwd},
       {"px_conv1_bwd", &g_tune.px_conv1_bwd},
       {"specialize", &g_tune.specialize}, {"ablate", &g_tune.ablate},
-      {"deterministic", &g_tune.deterministic}};
+      {"deterministic", &g_tune.deterministic},
+      {"shallow_bf16_grid", &g_tune.shallow_bf16_grid}};
   for (auto& e : table) {
     if (std::strcmp(e.k, key) == 0) {
       const int old = *e.v;
@@ -1756,10 +1758,10 @@ bool with_geo(int H, int W, int R, F&& f) {
 
 // Launch records, one per launcher family (launch_info()).
 enum Family { kResConvFwd, kResBlockFwd, kConvPoolFwd, kConv1PoolFwd,
-              kResConvBwd, kPoolConvBwd, kConv1PoolBwd, kFamilies };
+              kResConvBwd, kPoolConvBwd, kConv1PoolBwd, kShallowBf16, kFamilies };
 constexpr const char* kFamilyName[kFamilies] = {
     "res_conv_fwd", "res_block_fwd", "conv_pool_fwd", "conv1_pool_fwd",
-    "res_conv_bwd", "pool_conv_bwd", "conv1_pool_bwd"};
+    "res_conv_bwd", "pool_conv_bwd", "conv1_pool_bwd", "shallow_bf16"};
 LaunchInfo g_launch[kFamilies] = {};
 int g_last_family = -1;
 void note_launch(Family f, int grid, int grid_max, int ntiles, int rows,
@@ -1808,6 +1810,18 @@ LaunchInfo launch_info(const char* family) {
 }
 
 int res_conv_rows(int H, int W) { return rows_for(H, W, 32, g_tune.px_res_fwd); }
+
+// conv_shallow_bf16.hip: one workgroup per CU (its LDS fills one), capped by
+// conv_tune("shallow_bf16_grid"); its launch record.
+int shallow_bf16_grid_max() {
+  int grid_max = 0;
+  grid_for(1, 160 * 1024, 1, &grid_max);
+  const int cap = g_tune.shallow_bf16_grid;
+  return cap > 0 && cap < grid_max ? cap : grid_max;
+}
+void shallow_bf16_note(int grid, int grid_max, int ntiles) {
+  note_launch(kShallowBf16, grid, grid_max, ntiles, 0, true);
+}
 
 void res_block_fwd_launch(const void* x, const float* w1, const float* b1,
                           const float* w2, const float* b2, void* t, void* y,

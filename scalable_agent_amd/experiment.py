@@ -222,6 +222,27 @@ def _log_torso_blocks(flags, model):
            'apply: %s)', used, asked, why)
 
 
+def _log_torso_precision(model):
+  """The precision of the torso the inference model's steps actually run."""
+  agent = model.agent
+  used = model.torso_precision
+  asked = 'bf16' if str(agent.compute_dtype) == 'torch.bfloat16' else 'fp32'
+  frame = 'x'.join(str(d) for d in agent.frame_shape)
+  if used == 'torch':
+    log.info('actor inference torso precision: torch (%s compute, the torch '
+             'backend)', asked)
+  elif asked == 'bf16' and used == 'fp32':
+    log.info('actor inference torso precision: fp32 (bf16 inference asked for: '
+             'no bf16 %s torso kernel takes %s frames; the exact-fp32 torso '
+             'and core run)', agent.torso_kind, frame)
+  elif used == 'bf16' and agent.torso_kind == 'shallow':
+    log.info('actor inference torso precision: bf16 (x / 255 and the three '
+             'convs of the shallow torso in one bf16 MFMA launch on %s frames)',
+             frame)
+  else:
+    log.info('actor inference torso precision: %s', used)
+
+
 def _log_actor_core(flags, model):
   """Which core the inference model's steps run (--actor_core)."""
   asked = getattr(flags, 'actor_core', 'ops')
@@ -668,6 +689,7 @@ def train(flags):
         if lane == 0:
           _log_actor_core(flags, lane_model)
           _log_torso_blocks(flags, lane_model)
+          _log_torso_precision(lane_model)
         servers.append(BoardServer(lane_model, lane_board,
                                    gather_us=flags.inference_gather_us,
                                    depth=flags.inference_board_depth))
@@ -691,6 +713,7 @@ def train(flags):
                                          seed=flags.seed + 17 * rank)
     _log_actor_core(flags, model)
     _log_torso_blocks(flags, model)
+    _log_torso_precision(model)
     model.publish(learner.flat.params)
     infer = inference_lib.make_batched_infer(
         model, flags.inference_min_batch, flags.inference_max_batch,

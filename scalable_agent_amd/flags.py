@@ -107,7 +107,13 @@ def build_parser() -> argparse.ArgumentParser:
                  choices=['auto', 'fp32', 'bf16'],
                  help='Actor-inference compute dtype (auto = --dtype); bf16 '
                       'trades behaviour-policy precision (V-trace corrects '
-                      'for the policy lag either way) for actor throughput.')
+                      'for the policy lag either way) for actor throughput.  '
+                      'The deep torso runs its fused bf16 kernels; the shallow '
+                      'torso runs its actor steps on a one-launch bf16 MFMA '
+                      'kernel for 72x96, 84x84 and 72x128 frames with up to 4 '
+                      'channels (other frames keep the exact-fp32 torso and '
+                      'core; the start-up log names the precision that '
+                      'runs).')
   p.add_argument('--actor_core', default='ops', choices=['ops', 'fused'],
                  help='Actor-inference core step of an fp32 HIP agent: ops = '
                       'x-projection GEMM, LSTM step and heads + sampler '

@@ -134,6 +134,13 @@ class InferenceModel(object):
             fused(self._gen, self.device.type == 'cuda') else 'ops')
 
   @property
+  def torso_precision(self):
+    """'bf16' / 'fp32' (HIP kernels) or 'torch': the torso this model's steps
+    actually run (Agent.inference_torso_precision)."""
+    prec = getattr(self.agent, 'inference_torso_precision', None)
+    return 'torch' if prec is None else prec(self.device.type == 'cuda')
+
+  @property
   def torso_blocks(self):
     """The form this model's torso runs: 'heads' (as 'stage', and the stage-0
     and / or stage-1 head as one kernel: Agent(torso_blocks='heads') where the

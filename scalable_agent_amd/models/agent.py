@@ -251,6 +251,13 @@ class Agent(nn.Module):
       from .. import ops
       if _bf16_torso_ready(self):
         return ops.torso_forward(self, frames)
+      # actor inference of a bf16 shallow agent: the whole conv torso in one
+      # bf16 MFMA launch (bf16 features: the bf16 FC GEMM and core follow);
+      # the learner and any call under autograd take the fp32 kernels
+      if (self._shallow_bf16_agent() and not torch.is_grad_enabled() and
+          frames.shape[0] <= ops.conv.FUSED_BLOCK_MAX_FRAMES and
+          ops.conv.shallow_bf16_form(frames.shape[1:], frames.shape[0])):
+        return ops.torso_forward_shallow_bf16(self, frames)
       # exact fp32 kernels (also for a bf16 agent whose shape the bf16
       # kernels do not cover); unsupported shapes raise, never fall back
       return ops.torso_forward_f32(self, frames)
@@ -476,6 +483,11 @@ class Agent(nn.Module):
     dev = self.lstm_kernel.device
     cache = {'w4': torch.empty(CORE_SIZE * 4 * CORE_SIZE, device=dev),
              'w16': None, 'w0pad': None}
+    if (self._shallow_bf16_agent() and
+        self.inference_torso_precision() == 'bf16'):
+      # the shallow torso's conv weights in the bf16 kernel's operand layout
+      from ..ops import conv
+      cache['wsh16'] = conv.shallow_bf16_pack(self)
     if (self.compute_dtype == torch.float32 and self.torso_kind == 'deep' and
         self.frame_shape[2] < 4):
       # the fp32 torso's stage-0 weights padded to the 4-channel image
@@ -518,12 +530,32 @@ class Agent(nn.Module):
       w16_fc, wx16 = cache['w16']
       w16_fc.copy_(self.linear_w)
       wx16.copy_(self.lstm_kernel[:wx16.shape[0]])
+    if cache.get('wsh16') is not None:
+      ops.conv.shallow_bf16_pack(self, out=cache['wsh16'])
     if cache.get('wpk') is not None:
       ops.actor_core.actor_core_pack(self.lstm_kernel, self.num_actions,
                                      out=cache['wpk'])
     if cache.get('wb0') is not None:
       cache['wb0'][0].copy_(self.baseline_w[:, :1])
       cache['wb0'][1].copy_(self.baseline_b[:1])
+
+  def _shallow_bf16_agent(self):
+    """A HIP shallow agent asked to compute in bf16."""
+    return (self.backend == 'hip' and self.torso_kind == 'shallow' and
+            self.compute_dtype == torch.bfloat16)
+
+  def inference_torso_precision(self, cuda=True):
+    """The precision of the torso a no-grad forward of a board's worth (<=
+    ops.conv.FUSED_BLOCK_MAX_FRAMES) of this agent's frames runs: 'bf16' /
+    'fp32' (HIP kernels) or 'torch'.  Differs from torso_precision() (the
+    learner's) for a bf16 shallow agent: its inference torso is the one-launch
+    bf16 kernel where that takes the frame, else the fp32 kernels."""
+    if self.backend != 'hip' or not cuda:
+      return 'torch'
+    if self._shallow_bf16_agent():
+      from ..ops import conv
+      return 'bf16' if conv.shallow_bf16_form(self.frame_shape) else 'fp32'
+    return torso_precision(self)
 
   def actor_core_fused(self, generator, cuda=True):
     """True when `actor_core='fused'` is honoured for a T = 1 no-grad step

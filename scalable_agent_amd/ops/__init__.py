@@ -12,6 +12,7 @@ from .rmsprop import poison_on_error, rmsprop_step  # noqa: F401
 from .vtrace_loss import vtrace_loss, vtrace_fused_forward  # noqa: F401
 from .lstm import lstm_unroll  # noqa: F401
 from .conv import torso_forward, linear_relu  # noqa: F401
+from .conv import torso_forward_shallow_bf16  # noqa: F401
 from .conv_f32 import torso_forward_f32, linear_relu_f32  # noqa: F401
 from .core import core_lstm  # noqa: F401
 from .lang import language_lstm  # noqa: F401

@@ -9,6 +9,12 @@ Backward per residual block: two fused dgrad+wgrad+bias passes; per stage head
 one pass that gathers the pooled gradient through the saved argmax in LDS.
 All activations NHWC bf16; weights/biases fp32 master copies (TF HWIO); their
 gradients accumulate in fp32 directly inside the kernels.
+
+The SHALLOW torso has one bf16 kernel, for actor inference only
+(csrc/kernels/conv_shallow_bf16.hip, torso_forward_shallow_bf16): x / 255 and
+the three convs (8x8/4, 4x4/2, 3x3/2) of a no-grad forward in one launch on
+bf16 MFMA, uint8 frames in, bf16 features out.  It has no backward: the
+learner, and supports() / TORSO_READY, stay deep-only.
 """
 
 import os
@@ -184,6 +190,55 @@ def torso_forward(agent, frames):
                             frames.shape[0] <= FUSED_BLOCK_MAX_FRAMES)
         else _DeepTorso)
   return _chunked(fn, frames.contiguous(), deep_param_list(agent))
+
+
+SHALLOW_BF16_FRAMES = ((72, 96), (84, 84), (72, 128))
+
+
+def shallow_bf16_form(frame_shape, frames=1):
+  """True where shallow_bf16_fwd takes `frames` uint8 frames of this [H, W, C]
+  shape: 72x96, 84x84 or 72x128 with C <= 4, 1 <= frames <=
+  FUSED_BLOCK_MAX_FRAMES.  Host arithmetic only (the binding's
+  shallow_bf16_form says the same)."""
+  if len(frame_shape) != 3:
+    return False
+  h, w, c = (int(d) for d in frame_shape)
+  return ((h, w) in SHALLOW_BF16_FRAMES and 1 <= c <= 4 and
+          1 <= int(frames) <= FUSED_BLOCK_MAX_FRAMES)
+
+
+def shallow_bf16_pack(agent, out=None):
+  """The shallow agent's three conv weights in the kernel's bf16 B-operand
+  layout (shallow_bf16_pack); out: three tensors to refresh in place."""
+  from .conv_f32 import shallow_param_list
+  p = shallow_param_list(agent)
+  packed = ext().shallow_bf16_pack(p[0].detach(), p[2].detach(), p[4].detach())
+  if out is None:
+    return tuple(packed)
+  for dst, src in zip(out, packed):
+    dst.copy_(src)
+  return out
+
+
+def torso_forward_shallow_bf16(agent, frames):
+  """uint8 frames [N,H,W,C] -> ReLU'd conv features [N, flat] (bf16) of the
+  shallow torso in one launch; no autograd.  Uses the agent's
+  _inference_cache['wsh16'] (packed once per weight publish) when present,
+  else packs per call.  Raises where the kernel declines."""
+  if agent.torso_kind != 'shallow':
+    raise NotImplementedError('shallow bf16 torso on a %r agent' %
+                              (agent.torso_kind,))
+  if frames.dtype != torch.uint8:
+    raise TypeError('HIP torso expects uint8 frames, got %s' % frames.dtype)
+  from .conv_f32 import shallow_param_list
+  cache = getattr(agent, '_inference_cache', None)
+  wp = None if cache is None else cache.get('wsh16')
+  if wp is None:
+    wp = shallow_bf16_pack(agent)
+  p = shallow_param_list(agent)
+  x = ext().shallow_bf16_fwd(frames.contiguous(), wp[0], p[1].detach(),
+                             wp[1], p[3].detach(), wp[2], p[5].detach())
+  return x.reshape(x.shape[0], -1)
 
 
 def linear_relu(x, w, b):
