@@ -36,82 +36,17 @@
 // h_in is every workgroup's A operand, so h2 is a distinct buffer.  The
 // board's commit target may be h_in / c_in themselves: the finisher writes a
 // tile's rows only after every reader of those rows has taken its ticket.
-#include "head_sample.h"
-#include "launchers.h"
+#include "actor_core_tail.h"
 
 namespace sa {
 namespace {
 
+using namespace actor_core;  // ActorCoreArgs, the gate math, the tail
+
 typedef float f4v __attribute__((ext_vector_type(4)));
 
-constexpr int kH = 256;
 constexpr int kNW = 8;       // waves per workgroup
 constexpr int kNSMax = 20;   // MFMA k-steps per wave: (K + 256) / 4 / 8 <= 20
-constexpr int kRows = 16;    // rows per tile
-
-struct ActorCoreArgs {
-  const float* h_aug;   // [R, ld]
-  const uint8_t* done;  // [R]
-  const float* c_in;    // [R, 256]
-  const float* h_in;    // [R, 256]
-  const float* wpk;     // [64][kp][16]: rows [0, K) of W_x, rows kh0.. of W_h
-  const float* b_lstm;  // [1024]
-  const float* wp;      // [256, A]
-  const float* bp;      // [A]
-  const float* wb;      // [256, Kv] (head 0 is read)
-  const float* bb;      // [Kv]
-  float* c2;            // [R, 256]
-  float* h2;            // [R, 256]
-  float* logits;        // [R, A]
-  float* baseline;      // [R]
-  int64_t* action;      // [R]
-  unsigned* tickets;    // [row tiles], zero between launches
-  unsigned long long* counter;  // nullptr or {offset, waves done}
-  unsigned long long seed, offset;
-  int R, ld, K, kh0, kp, A, Kv;
-  // board epilogue (out == nullptr: none)
-  const float* mask;    // [R]
-  float* c;             // commit targets (may be c_in / h_in)
-  float* h;
-  uint32_t* out;
-  int off_dw[5];        // action, logits, baseline, c, h
-  int M, slot_dw, masked_only;
-};
-
-__device__ __forceinline__ float sigm(float x) { return 1.f / (1.f + __expf(-x)); }
-
-// heads + Gumbel-max sample (+ board commit / packing) of one finished row
-template <int W>
-__device__ __forceinline__ void finish_row(const ActorCoreArgs& a, int row, int lane,
-                                           unsigned long long offset) {
-  const int A = a.A;
-  const float4 x = reinterpret_cast<const float4*>(a.h2 + static_cast<int64_t>(row) * kH)[lane];
-  const HeadSample hs = head_sample_row<W, false>(x, a.wp, a.bp, a.wb, a.bb, a.Kv, a.logits, A,
-                                                  a.seed, offset, row, lane);
-  const float mine = hs.logit, base = hs.baseline;
-  const int idx = hs.action;
-  if (lane == 0) {
-    a.baseline[row] = base;
-    a.action[row] = idx;
-  }
-  if (a.out == nullptr) return;
-  // board epilogue of this row (board_epilogue_kernel's semantics)
-  const bool keep = a.mask[row] > 0.f;
-  const float4 cv = reinterpret_cast<const float4*>(a.c2 + static_cast<int64_t>(row) * kH)[lane];
-  if (keep) {
-    reinterpret_cast<float4*>(a.c + static_cast<int64_t>(row) * kH)[lane] = cv;
-    reinterpret_cast<float4*>(a.h + static_cast<int64_t>(row) * kH)[lane] = x;
-  }
-  if (a.masked_only && !keep) return;  // uniform per wave
-  const int s = row / a.M, m = row - s * a.M;
-  uint32_t* dst = a.out + static_cast<int64_t>(s) * a.slot_dw;
-  if (lane < 2) dst[a.off_dw[0] + m * 2 + lane] = lane == 0 ? static_cast<uint32_t>(idx) : 0u;
-  if (lane < A) dst[a.off_dw[1] + m * A + lane] = __float_as_uint(mine);
-  if (lane == 0) dst[a.off_dw[2] + m] = __float_as_uint(base);
-  reinterpret_cast<float4*>(dst + a.off_dw[3] + m * kH)[lane] = cv;
-  reinterpret_cast<float4*>(dst + a.off_dw[4] + m * kH)[lane] = x;
-  if (a.masked_only) __threadfence_system();
-}
 
 // W: the finisher's head accumulator width (32: A <= 32, 64: A <= 63); the
 // launcher picks the instance, nothing before the finisher depends on it
@@ -191,56 +126,13 @@ __global__ __launch_bounds__(64 * kNW) void actor_core_step_kernel(ActorCoreArgs
   }
   __syncthreads();
   if (tid < 4 * kRows && egr < R) {
-    const float ekeep = edone ? 0.f : 1.f;
-    const float i = sigm(g_s[er][eu * 4 + 0] + bi);
-    const float g = tanhf(g_s[er][eu * 4 + 1] + bc);
-    const float f = sigm(g_s[er][eu * 4 + 2] + bf + 1.0f);
-    const float o = sigm(g_s[er][eu * 4 + 3] + bo);
-    const float c = f * ekeep * cp + i * g;
-    const int64_t hj = static_cast<int64_t>(egr) * kH + ej;
-    a.c2[hj] = c;
-    a.h2[hj] = o * tanhf(c);
+    lstm_cell_store(a, static_cast<int64_t>(egr) * kH + ej, g_s[er][eu * 4 + 0],
+                    g_s[er][eu * 4 + 1], g_s[er][eu * 4 + 2], g_s[er][eu * 4 + 3], bi, bc, bf,
+                    bo, cp, edone);
   }
   // publish this workgroup's c2 / h2 slice and take a ticket of the row tile
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-  if (tid == 0) {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    const unsigned prev = __hip_atomic_fetch_add(a.tickets + tile, 1u, __ATOMIC_RELAXED,
-                                                 __HIP_MEMORY_SCOPE_AGENT);
-    const int last = prev == gridDim.x - 1;
-    if (last) {
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      // re-arm for the next launch (nobody else touches it in this one)
-      __hip_atomic_store(a.tickets + tile, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    last_s = last;
-  }
-  __syncthreads();
-  if (!last_s) return;
-  // ---- the row tile's last arriver: every c2 / h2 byte of the tile is
-  // visible behind the acquire above
-  unsigned long long offset = a.offset;
-  if (a.counter != nullptr)
-    offset = __hip_atomic_load(a.counter, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  for (int rr = wave; rr < kRows; rr += kNW) {
-    const int row = r0 + rr;
-    if (row < R) finish_row<W>(a, row, lane, offset);
-  }
-  // the sampler's counter pair {offset, waves done}: every finishing wave
-  // counts itself after its sampling; the last one of the launch stores
-  // offset + 1 and re-arms the count (actor_head_sample_kernel's protocol)
-  if (a.counter != nullptr && lane == 0) {
-    const unsigned long long waves = static_cast<unsigned long long>(gridDim.y) * kNW;
-    const unsigned long long done = __hip_atomic_fetch_add(
-        a.counter + 1, 1ull, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
-    if (done == waves - 1) {
-      __hip_atomic_store(a.counter, offset + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      __hip_atomic_store(a.counter + 1, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-  }
+  // (the tile's last arriver finishes its rows: actor_core_tail.h)
+  publish_and_finish<W, kNW>(a, tile, &last_s);
 }
 
 // lstm_kernel [f_in + 256, 1024] -> the step kernel's B operand
@@ -275,41 +167,7 @@ void actor_core_pack_launch(const float* w, float* wpk, int f_in, int kmax, hipS
 
 void actor_core_step_launch(const ActorCoreStep& p, hipStream_t stream) {
   if (p.R <= 0) return;
-  ActorCoreArgs a{};
-  a.h_aug = p.h_aug;
-  a.done = p.done;
-  a.c_in = p.c_in;
-  a.h_in = p.h_in;
-  a.wpk = p.wpk;
-  a.b_lstm = p.b_lstm;
-  a.wp = p.wp;
-  a.bp = p.bp;
-  a.wb = p.wb;
-  a.bb = p.bb;
-  a.c2 = p.c2;
-  a.h2 = p.h2;
-  a.logits = p.logits;
-  a.baseline = p.baseline;
-  a.action = p.action;
-  a.tickets = p.tickets;
-  a.counter = p.counter;
-  a.seed = p.seed;
-  a.offset = p.offset;
-  a.R = p.R;
-  a.ld = p.ld;
-  a.K = p.K;
-  a.kh0 = p.kmax;
-  a.kp = p.kmax + kH;
-  a.A = p.A;
-  a.Kv = p.Kv;
-  a.mask = p.mask;
-  a.c = p.c;
-  a.h = p.h;
-  a.out = static_cast<uint32_t*>(p.out);
-  for (int f = 0; f < 5; ++f) a.off_dw[f] = p.off_dw[f];
-  a.M = p.M;
-  a.slot_dw = p.slot_dw;
-  a.masked_only = p.masked_only;
+  const ActorCoreArgs a = make_args(p);
   auto kernel = p.A <= 32 ? actor_core_step_kernel<32> : actor_core_step_kernel<64>;
   hipLaunchKernelGGL(kernel, dim3(kH / 4, (p.R + kRows - 1) / kRows), dim3(64 * kNW), 0, stream,
                      a);

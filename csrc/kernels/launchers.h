@@ -262,6 +262,27 @@ void actor_core_step_launch(const ActorCoreStep& p, hipStream_t stream);
 void actor_core_pack_launch(const float* w, float* wpk, int f_in, int kmax,
                             hipStream_t stream);
 
+// ---- actor_core_bf16.hip ---------------------------------------------------
+// The same step on v_mfma_f32_16x16x32_bf16 (bf16 operands, fp32 accumulate;
+// rounding points in the file header).  Takes an ActorCoreStep whose `wpk` is
+// unused, `K` is the true width of h_aug's column range (any K >= 257 + A,
+// ld >= K, no alignment asked of h_aug) and `kmax` (% 32 == 0, >= K,
+// <= actor_core_bf16_max_k()) the W_x rows of wpk16.
+struct ActorCoreBf16Info {
+  int grid_x, grid_y;  // column groups x 16-row tiles
+  int ksteps;          // MFMA k-steps of one gate column: kpad / 32 + 8
+  int kpad;            // K padded to 32
+  int width;           // the finisher's head instance: 32 (A <= 32) or 64
+};
+ActorCoreBf16Info actor_core_bf16_info(int R, int K, int A);
+int actor_core_bf16_max_k();
+void actor_core_bf16_step_launch(const ActorCoreStep& p, const uint16_t* wpk16,
+                                 hipStream_t stream);
+// lstm_kernel [f_in + 256, 1024] -> wpk16 [(kmax + 256) * 1024] bf16 (RNE);
+// rows [f_in, kmax) zero
+void actor_core_bf16_pack_launch(const float* w, uint16_t* wpk16, int f_in, int kmax,
+                                 hipStream_t stream);
+
 // ---- calibration ----------------------------------------------------------
 void noop_launch(int blocks, int threads, int* p, hipStream_t s);
 

@@ -360,22 +360,39 @@ void actor_core_pack(at::Tensor kernel, int64_t f_in, at::Tensor wpk) {
 // epi_mask > 0 and {action, logits, baseline, c2, h2} are packed into epi_out
 // (or the device-accessible address epi_out_addr: masked rows only) as
 // board_epilogue does.  -> {action, logits, baseline, c2, h2}
-std::vector<at::Tensor> actor_core_step(
-    at::Tensor h_aug, at::Tensor done, at::Tensor c_in, at::Tensor h_in, at::Tensor wpk,
-    at::Tensor b_lstm, at::Tensor wp, at::Tensor bp, at::Tensor wb, at::Tensor bb,
-    at::Tensor tickets, int64_t seed, int64_t offset, c10::optional<at::Tensor> counter,
-    c10::optional<at::Tensor> epi_mask, std::vector<int64_t> epi_offs,
-    c10::optional<at::Tensor> epi_out, int64_t epi_M, int64_t epi_slot_bytes,
-    int64_t epi_out_addr) {
-  LB_CHECK(h_aug); LB_CHECK(done); LB_CHECK(c_in); LB_CHECK(h_in); LB_CHECK(wpk);
+//
+// bf16 (kernels/actor_core_bf16.hip): wpk is actor_core_bf16_pack's, h_aug
+// [R, K] may be a column range of a wider row-major matrix (any K >= 257 + A,
+// unit column stride), and `outs` may name the five outputs: contiguous
+// tensors of >= R rows whose first R rows are written and returned.
+std::vector<at::Tensor> actor_core_step_any(
+    bool bf16, at::Tensor h_aug, at::Tensor done, at::Tensor c_in, at::Tensor h_in,
+    at::Tensor wpk, at::Tensor b_lstm, at::Tensor wp, at::Tensor bp, at::Tensor wb,
+    at::Tensor bb, at::Tensor tickets, int64_t seed, int64_t offset,
+    c10::optional<at::Tensor> counter, c10::optional<at::Tensor> epi_mask,
+    std::vector<int64_t> epi_offs, c10::optional<at::Tensor> epi_out, int64_t epi_M,
+    int64_t epi_slot_bytes, int64_t epi_out_addr,
+    c10::optional<std::vector<at::Tensor>> outs) {
+  LB_CHECK(done); LB_CHECK(c_in); LB_CHECK(h_in); LB_CHECK(wpk);
   LB_CHECK(b_lstm); LB_CHECK(wp); LB_CHECK(bp); LB_CHECK(wb); LB_CHECK(bb); LB_CHECK(tickets);
-  LB_F32(h_aug); LB_F32(c_in); LB_F32(h_in); LB_F32(wpk); LB_F32(b_lstm);
+  LB_F32(h_aug); LB_F32(c_in); LB_F32(h_in); LB_F32(b_lstm);
   LB_F32(wp); LB_F32(bp); LB_F32(wb); LB_F32(bb);
   TORCH_CHECK(h_aug.dim() == 2, "h_aug must be [R, K]");
   const int64_t R = h_aug.size(0), K = h_aug.size(1);
   const int64_t kmax = wpk.numel() / 1024 - 256;
-  TORCH_CHECK(wpk.numel() == (kmax + 256) * 1024 && K % 16 == 0 && K >= 16 && K <= kmax &&
-                  kmax <= sa::actor_core_max_k(), "h_aug width / packed weights mismatch");
+  if (bf16) {
+    LB_BF16(wpk);
+    TORCH_CHECK(h_aug.is_cuda() && (R <= 1 || h_aug.stride(0) >= K) && h_aug.stride(1) == 1,
+                "h_aug must be a row-major GPU matrix (or a column range of one)");
+    TORCH_CHECK(wpk.numel() == (kmax + 256) * 1024 && kmax % 32 == 0 && K <= kmax &&
+                    kmax <= sa::actor_core_bf16_max_k() &&
+                    reinterpret_cast<uintptr_t>(wpk.data_ptr()) % 16 == 0,
+                "h_aug width / packed bf16 weights mismatch");
+  } else {
+    LB_CHECK(h_aug); LB_F32(wpk);
+    TORCH_CHECK(wpk.numel() == (kmax + 256) * 1024 && K % 16 == 0 && K >= 16 && K <= kmax &&
+                    kmax <= sa::actor_core_max_k(), "h_aug width / packed weights mismatch");
+  }
   TORCH_CHECK(done.numel() == R && c_in.dim() == 2 && c_in.size(0) == R && c_in.size(1) == 256 &&
                   c_in.sizes() == h_in.sizes() && b_lstm.numel() == 1024, "core shapes");
   TORCH_CHECK(wp.dim() == 2 && wp.size(0) == 256 && wb.dim() == 2 && wb.size(0) == 256,
@@ -397,11 +414,32 @@ std::vector<at::Tensor> actor_core_step(
     p.counter = reinterpret_cast<unsigned long long*>(counter->data_ptr());
   }
   const c10::DeviceGuard guard(h_aug.device());
-  auto action = at::empty({R}, h_aug.options().dtype(at::kLong));
-  auto logits = at::empty({R, A}, h_aug.options());
-  auto baseline = at::empty({R}, h_aug.options());
-  auto c2 = at::empty({R, 256}, h_aug.options());
-  auto h2 = at::empty({R, 256}, h_aug.options());
+  at::Tensor action, logits, baseline, c2, h2;
+  if (outs.has_value()) {
+    TORCH_CHECK(outs->size() == 5, "outs: {action, logits, baseline, c2, h2}");
+    const int64_t cols[5] = {1, A, 1, 256, 256};
+    for (int f = 0; f < 5; ++f) {
+      const at::Tensor& t = (*outs)[f];
+      LB_CHECK(t);
+      TORCH_CHECK(t.scalar_type() == (f == 0 ? at::kLong : at::kFloat) && t.dim() >= 1 &&
+                      t.size(0) >= R && t.numel() == t.size(0) * cols[f],
+                  "outs: int64 [>= R], fp32 [>= R, A], [>= R], [>= R, 256] x 2");
+    }
+    TORCH_CHECK(reinterpret_cast<uintptr_t>((*outs)[3].data_ptr()) % 16 == 0 &&
+                    reinterpret_cast<uintptr_t>((*outs)[4].data_ptr()) % 16 == 0,
+                "outs: c2 / h2 must be 16-byte aligned");
+    action = (*outs)[0].narrow(0, 0, R);
+    logits = (*outs)[1].narrow(0, 0, R);
+    baseline = (*outs)[2].narrow(0, 0, R);
+    c2 = (*outs)[3].narrow(0, 0, R);
+    h2 = (*outs)[4].narrow(0, 0, R);
+  } else {
+    action = at::empty({R}, c_in.options().dtype(at::kLong));
+    logits = at::empty({R, A}, c_in.options());
+    baseline = at::empty({R}, c_in.options());
+    c2 = at::empty({R, 256}, c_in.options());
+    h2 = at::empty({R, 256}, c_in.options());
+  }
   if (epi_mask.has_value()) {
     LB_CHECK(*epi_mask); LB_F32(*epi_mask);
     TORCH_CHECK(epi_out.has_value(), "epilogue needs the output block");
@@ -430,7 +468,7 @@ std::vector<at::Tensor> actor_core_step(
   p.done = mask_ptr(done);
   p.c_in = c_in.data_ptr<float>();
   p.h_in = h_in.data_ptr<float>();
-  p.wpk = wpk.data_ptr<float>();
+  if (!bf16) p.wpk = wpk.data_ptr<float>();
   p.b_lstm = b_lstm.data_ptr<float>();
   p.wp = wp.data_ptr<float>();
   p.bp = bp.data_ptr<float>();
@@ -445,13 +483,72 @@ std::vector<at::Tensor> actor_core_step(
   p.seed = static_cast<unsigned long long>(seed);
   p.offset = static_cast<unsigned long long>(offset);
   p.R = static_cast<int>(R);
-  p.ld = static_cast<int>(K);
+  p.ld = static_cast<int>(R > 1 ? h_aug.stride(0) : K);
   p.K = static_cast<int>(K);
   p.kmax = static_cast<int>(kmax);
   p.A = static_cast<int>(A);
   p.Kv = static_cast<int>(Kv);
-  sa::actor_core_step_launch(p, stream());
+  if (bf16)
+    sa::actor_core_bf16_step_launch(p, reinterpret_cast<const uint16_t*>(wpk.data_ptr()),
+                                    stream());
+  else
+    sa::actor_core_step_launch(p, stream());
   return {action, logits, baseline, c2, h2};
+}
+
+std::vector<at::Tensor> actor_core_step(
+    at::Tensor h_aug, at::Tensor done, at::Tensor c_in, at::Tensor h_in, at::Tensor wpk,
+    at::Tensor b_lstm, at::Tensor wp, at::Tensor bp, at::Tensor wb, at::Tensor bb,
+    at::Tensor tickets, int64_t seed, int64_t offset, c10::optional<at::Tensor> counter,
+    c10::optional<at::Tensor> epi_mask, std::vector<int64_t> epi_offs,
+    c10::optional<at::Tensor> epi_out, int64_t epi_M, int64_t epi_slot_bytes,
+    int64_t epi_out_addr) {
+  return actor_core_step_any(false, h_aug, done, c_in, h_in, wpk, b_lstm, wp, bp, wb, bb,
+                             tickets, seed, offset, counter, epi_mask, epi_offs, epi_out, epi_M,
+                             epi_slot_bytes, epi_out_addr, c10::nullopt);
+}
+
+std::vector<at::Tensor> actor_core_bf16_step(
+    at::Tensor h_aug, at::Tensor done, at::Tensor c_in, at::Tensor h_in, at::Tensor wpk16,
+    at::Tensor b_lstm, at::Tensor wp, at::Tensor bp, at::Tensor wb, at::Tensor bb,
+    at::Tensor tickets, int64_t seed, int64_t offset, c10::optional<at::Tensor> counter,
+    c10::optional<at::Tensor> epi_mask, std::vector<int64_t> epi_offs,
+    c10::optional<at::Tensor> epi_out, int64_t epi_M, int64_t epi_slot_bytes,
+    int64_t epi_out_addr, c10::optional<std::vector<at::Tensor>> outs) {
+  return actor_core_step_any(true, h_aug, done, c_in, h_in, wpk16, b_lstm, wp, bp, wb, bb,
+                             tickets, seed, offset, counter, epi_mask, epi_offs, epi_out, epi_M,
+                             epi_slot_bytes, epi_out_addr, outs);
+}
+
+// lstm_kernel [f_in + 256, 1024] fp32 -> wpk16, the bf16 B operand of
+// actor_core_bf16_step: W_x rows padded to kmax = wpk16.numel() / 1024 - 256
+// (% 32 == 0), then W_h.  One launch, no scratch.
+void actor_core_bf16_pack(at::Tensor kernel, int64_t f_in, at::Tensor wpk16) {
+  LB_CHECK(kernel); LB_CHECK(wpk16); LB_F32(kernel); LB_BF16(wpk16);
+  TORCH_CHECK(kernel.dim() == 2 && kernel.size(0) == f_in + 256 && kernel.size(1) == 1024,
+              "kernel must be [f_in + 256, 1024]");
+  const int64_t kmax = wpk16.numel() / 1024 - 256;
+  TORCH_CHECK(wpk16.numel() == (kmax + 256) * 1024 && kmax >= f_in && kmax % 32 == 0 &&
+                  kmax <= sa::actor_core_bf16_max_k() &&
+                  reinterpret_cast<uintptr_t>(wpk16.data_ptr()) % 16 == 0,
+              "wpk16 must hold (kmax + 256) * 1024 bf16, f_in <= kmax % 32 == 0");
+  const c10::DeviceGuard guard(kernel.device());
+  sa::actor_core_bf16_pack_launch(kernel.data_ptr<float>(),
+                                  reinterpret_cast<uint16_t*>(wpk16.data_ptr()),
+                                  static_cast<int>(f_in), static_cast<int>(kmax), stream());
+}
+
+// Host only: the launch geometry actor_core_bf16_step takes for (R, K, A).
+pybind11::dict actor_core_bf16_info(int64_t R, int64_t K, int64_t A) {
+  const sa::ActorCoreBf16Info i = sa::actor_core_bf16_info(
+      static_cast<int>(R), static_cast<int>(K), static_cast<int>(A));
+  pybind11::dict d;
+  d["grid"] = pybind11::make_tuple(i.grid_x, i.grid_y);
+  d["ksteps"] = i.ksteps;
+  d["kpad"] = i.kpad;
+  d["width"] = i.width;
+  d["max_k"] = sa::actor_core_bf16_max_k();
+  return d;
 }
 
 // C[:, :N] (+)= op(A) op(B) with the fused epilogue of kernels/gemm_f32.h.
@@ -767,4 +864,18 @@ void register_learner_ops(pybind11::module& m) {
         pybind11::arg("epi_offs") = std::vector<int64_t>(),
         pybind11::arg("epi_out") = pybind11::none(), pybind11::arg("epi_M") = 1,
         pybind11::arg("epi_slot_bytes") = 0, pybind11::arg("epi_out_addr") = 0);
+  m.def("actor_core_bf16_pack", &actor_core_bf16_pack, pybind11::arg("kernel"),
+        pybind11::arg("f_in"), pybind11::arg("wpk16"));
+  m.def("actor_core_bf16_step", &actor_core_bf16_step, pybind11::arg("h_aug"),
+        pybind11::arg("done"), pybind11::arg("c_in"), pybind11::arg("h_in"),
+        pybind11::arg("wpk16"), pybind11::arg("b_lstm"), pybind11::arg("wp"),
+        pybind11::arg("bp"), pybind11::arg("wb"), pybind11::arg("bb"), pybind11::arg("tickets"),
+        pybind11::arg("seed"), pybind11::arg("offset"), pybind11::arg("counter") = pybind11::none(),
+        pybind11::arg("epi_mask") = pybind11::none(),
+        pybind11::arg("epi_offs") = std::vector<int64_t>(),
+        pybind11::arg("epi_out") = pybind11::none(), pybind11::arg("epi_M") = 1,
+        pybind11::arg("epi_slot_bytes") = 0, pybind11::arg("epi_out_addr") = 0,
+        pybind11::arg("outs") = pybind11::none());
+  m.def("actor_core_bf16_info", &actor_core_bf16_info, pybind11::arg("R"), pybind11::arg("K"),
+        pybind11::arg("A"));
 }

@@ -247,11 +247,16 @@ def _log_actor_core(flags, model):
   """Which core the inference model's steps run (--actor_core)."""
   asked = getattr(flags, 'actor_core', 'ops')
   used = model.actor_core
-  if asked == used:
-    log.info('actor inference core: %s', used)
+  if asked != used:
+    log.info('actor inference core: %s (--actor_core=%s needs an fp32 or bf16 '
+             'HIP agent on a GPU with at most 63 actions)', used, asked)
+  elif used == 'fused':
+    import torch
+    bf16 = getattr(model.agent, 'compute_dtype', None) == torch.bfloat16
+    log.info('actor inference core: fused (%s)',
+             'bf16 MFMA operands, fp32 accumulate' if bf16 else 'exact fp32')
   else:
-    log.info('actor inference core: %s (--actor_core=%s needs an fp32 HIP '
-             'agent on a GPU with at most 63 actions)', used, asked)
+    log.info('actor inference core: %s', used)
 
 
 class EpisodeLogger(object):

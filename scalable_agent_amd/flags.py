@@ -115,13 +115,21 @@ def build_parser() -> argparse.ArgumentParser:
                       'core; the start-up log names the precision that '
                       'runs).')
   p.add_argument('--actor_core', default='ops', choices=['ops', 'fused'],
-                 help='Actor-inference core step of an fp32 HIP agent: ops = '
+                 help='Actor-inference core step of a HIP agent: ops = '
                       'x-projection GEMM, LSTM step and heads + sampler '
                       'kernels; fused = ONE kernel after the torso-FC GEMM '
                       '(on an inference board it also commits the state and '
                       'packs the outputs).  Both take up to 63 actions (with '
-                      'more the actors sample with torch.multinomial).  bf16 '
-                      'inference runs ops.')
+                      'more the actors sample with torch.multinomial).  With '
+                      'bf16 inference fused is the bf16 MFMA kernel: it '
+                      'rounds the core input, the kept h and the LSTM weights '
+                      'to bf16 once and accumulates in fp32, so its steps are '
+                      'close to the bf16 ops steps, not bitwise equal.  '
+                      'Measured, neither fused kernel beats the kernels it '
+                      'replaces (bf16: 38 against 31 us at 76 rows, 44 '
+                      'against 37 us at 150, '
+                      'profiles/actor_core_bf16_step.txt), so ops stays the '
+                      'default.')
   p.add_argument('--torso_blocks', default='ops',
                  choices=['ops', 'fused', 'stage', 'heads', 'whole'],
                  help='Fused forms of the fp32 HIP torso in actor '

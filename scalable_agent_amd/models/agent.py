@@ -505,9 +505,17 @@ class Agent(nn.Module):
     if self.actor_core == 'fused' and self.num_actions <= ACTOR_MAX_ACTIONS:
       # [W_x[:K_max]; W_h] in the fused core step's B-operand layout
       from ..ops import actor_core
-      k_max = actor_core.packed_rows(self.num_actions)
-      cache['wpk'] = torch.empty((k_max + CORE_SIZE) * 4 * CORE_SIZE,
-                                 device=dev)
+      if self.compute_dtype == torch.bfloat16:
+        # the same in bf16, for the bf16 MFMA step
+        k_max = actor_core.packed_rows_bf16(self.num_actions)
+        cache['wpk16'] = torch.empty((k_max + CORE_SIZE) * 4 * CORE_SIZE,
+                                     dtype=torch.bfloat16, device=dev)
+      if (self.compute_dtype == torch.float32 or self._shallow_bf16_agent()):
+        # (a bf16 shallow agent's steps on frames its bf16 torso declines
+        # run the fp32 torso and core)
+        k_max = actor_core.packed_rows(self.num_actions)
+        cache['wpk'] = torch.empty((k_max + CORE_SIZE) * 4 * CORE_SIZE,
+                                   device=dev)
     if self.num_value_heads > 1:
       # value head 0 contiguous, for the one-head sampler kernel
       cache['wb0'] = (torch.empty(CORE_SIZE, 1, device=dev),
@@ -535,6 +543,9 @@ class Agent(nn.Module):
     if cache.get('wpk') is not None:
       ops.actor_core.actor_core_pack(self.lstm_kernel, self.num_actions,
                                      out=cache['wpk'])
+    if cache.get('wpk16') is not None:
+      ops.actor_core.actor_core_bf16_pack(self.lstm_kernel, self.num_actions,
+                                          out=cache['wpk16'])
     if cache.get('wb0') is not None:
       cache['wb0'][0].copy_(self.baseline_w[:, :1])
       cache['wb0'][1].copy_(self.baseline_b[:1])
@@ -559,12 +570,15 @@ class Agent(nn.Module):
 
   def actor_core_fused(self, generator, cuda=True):
     """True when `actor_core='fused'` is honoured for a T = 1 no-grad step
-    of CUDA tensors sampled from `generator`: fp32 HIP agent whose fused core
-    applies, at most ops.heads.ACTOR_MAX_ACTIONS (63) actions, a
-    PhiloxStream.  Otherwise the ops path runs."""
+    of CUDA tensors sampled from `generator`: fp32 or bf16 HIP agent whose
+    fused core applies, at most ops.heads.ACTOR_MAX_ACTIONS (63) actions, a
+    PhiloxStream.  Otherwise the ops path runs.  The step takes the dtype of
+    the torso's features: bf16 features run the bf16 MFMA kernel, whose
+    rounding is not the bf16 ops step's (ops/actor_core.py)."""
     from ..ops.heads import ACTOR_MAX_ACTIONS, PhiloxStream
     return (self.actor_core == 'fused' and self.backend == 'hip' and cuda and
-            self.compute_dtype == torch.float32 and self.fused_core_ready() and
+            self.compute_dtype in (torch.float32, torch.bfloat16) and
+            self.fused_core_ready() and
             self.num_actions <= ACTOR_MAX_ACTIONS and
             isinstance(generator, PhiloxStream))
 
@@ -630,20 +644,37 @@ class Agent(nn.Module):
       instr_enc = self.instruction_encoding(
           (instr[0].reshape(B, -1), instr[1].reshape(B)), B,
           frames.device).float().contiguous()
-    h_aug = ops.core.core_input_f32(
-        feats.contiguous(), self.linear_w, self.linear_b,
-        reward.reshape(B).to(torch.float32).contiguous(),
-        actions.reshape(B).to(torch.int64).contiguous(), self.num_actions,
-        instr_enc)
+    rewards = reward.reshape(B).to(torch.float32).contiguous()
+    last = actions.reshape(B).to(torch.int64).contiguous()
     cache = self._inference_cache
-    wpk = None if cache is None else cache.get('wpk')
-    if wpk is None:  # no inference cache: packed per call
-      wpk = ops.actor_core.actor_core_pack(self.lstm_kernel, self.num_actions)
+    # the step's dtype is the features': a bf16 agent's fp32 torso (frames its
+    # bf16 torso declines) is followed by the fp32 core, as on the ops path
+    bf16 = feats.dtype == torch.bfloat16
+    if bf16:
+      w16 = None if cache is None else cache.get('w16')
+      w16_fc = self.linear_w.to(torch.bfloat16) if w16 is None else w16[0]
+      h_aug, K = ops.core.core_input_bf16(
+          feats.contiguous(), w16_fc, self.linear_b, rewards, last,
+          self.num_actions, instr_enc)
+      h_aug = h_aug[:, :K]
+      wpk = None if cache is None else cache.get('wpk16')
+      if wpk is None:  # no inference cache: packed per call
+        wpk = ops.actor_core.actor_core_bf16_pack(self.lstm_kernel,
+                                                  self.num_actions)
+    else:
+      h_aug = ops.core.core_input_f32(
+          feats.contiguous(), self.linear_w, self.linear_b, rewards, last,
+          self.num_actions, instr_enc)
+      wpk = None if cache is None else cache.get('wpk')
+      if wpk is None:  # no inference cache: packed per call
+        wpk = ops.actor_core.actor_core_pack(self.lstm_kernel,
+                                             self.num_actions)
     c, h = core_state
     action, logits, baseline, c2, h2 = ops.actor_core_step(
         h_aug, done.reshape(B).to(torch.bool), c, h, wpk, self.lstm_bias,
         self.policy_w, self.policy_b, self.baseline_w, self.baseline_b,
-        generator, epilogue=epilogue)
+        generator, epilogue=epilogue,
+        dtype=torch.bfloat16 if bf16 else torch.float32)
     return AgentOutput(action.view(1, B), logits.view(1, B, -1),
                        baseline.view(1, B)), (c2, h2)
 

@@ -185,6 +185,25 @@ def core_input_f32(feats, w_fc, b_fc, rewards, actions, num_actions,
   return h_aug
 
 
+def core_input_bf16(feats, w16_fc, b_fc, rewards, actions, num_actions,
+                    instr_enc):
+  """The bf16 inference step's core input kept in fp32, for the bf16 fused
+  core step (which rounds it to bf16 once, on load): h_aug[:, :K] = [relu(
+  feats W_fc + b_fc), clip(r), one_hot(a), instr] from ONE bf16 MFMA GEMM
+  (bf16 feats and w16_fc, fp32 accumulate and output; bias + ReLU + the
+  core-input columns in its epilogue) plus the instruction copy.  K is the
+  true width: 257 + A, + 64 with an instruction.  -> (h_aug [N, ld >= K], K)."""
+  f_in = CORE + 1 + num_actions + 64
+  K = f_in if instr_enc is not None else f_in - 64
+  h_aug = torch.empty(feats.shape[0], (K + 15) // 16 * 16,
+                      dtype=torch.float32, device=feats.device)
+  ext().gemm_bf16(feats, w16_fc, False, False, h_aug, bias=b_fc, relu=True,
+                  aug_reward=rewards, aug_action=actions)
+  if instr_enc is not None:
+    h_aug[:, f_in - 64:f_in].copy_(instr_enc)
+  return h_aug, K
+
+
 class _CoreLSTMF32(torch.autograd.Function):
   """Reference-precision (fp32) variant: every product is the exact-fp32
   MFMA GEMM of kernels/gemm_f32.hip with its fused epilogue, the recurrence
