@@ -121,6 +121,71 @@ std::vector<at::Tensor> res_block_fwd(at::Tensor x, at::Tensor w1, at::Tensor b1
   return {t, y};
 }
 
+// ---- one-launch stages of the no-grad forward (stage_fwd_kernel) ----
+int stage_form(const at::Tensor& x, int64_t cin, int64_t cout) {
+  const int64_t N = x.size(0), H = x.size(1), W = x.size(2);
+  if (N > INT_MAX || H > INT_MAX || W > INT_MAX) return 0;
+  return sa::conv::stage_bf16_form(static_cast<int>(N), static_cast<int>(H),
+                                   static_cast<int>(W), static_cast<int>(cin),
+                                   static_cast<int>(cout));
+}
+
+at::Tensor stage_launch(const at::Tensor& x, const at::Tensor* w, const at::Tensor* b,
+                        const at::Tensor* const blk[8], int64_t C, int64_t pb_h,
+                        int64_t pb_w, bool last, const char* name) {
+  const int64_t CIN = x.size(3);
+  const float* wb[8];
+  for (int i = 0; i < 8; i += 2) {
+    check_w(*blk[i], *blk[i + 1], C, C);
+    TORCH_CHECK(blk[i + 1]->is_cuda(), "bias must be on the GPU");
+    wb[i] = blk[i]->data_ptr<float>();
+    wb[i + 1] = blk[i + 1]->data_ptr<float>();
+  }
+  if (w) TORCH_CHECK(b->is_cuda(), "bias must be on the GPU");
+  const int64_t N = x.size(0), H = x.size(1), W = x.size(2);
+  // the pool's pad_before is 0 or 1 (TF SAME, 3x3/2); an odd width needs 1
+  TORCH_CHECK(pb_h >= 0 && pb_h <= 1 && pb_w >= (w ? (W & 1) : 0) && pb_w <= 1,
+              name, ": pb_h / pb_w must be the TF-SAME pad_before of the 3x3/2 pool");
+  TORCH_CHECK(stage_form(x, CIN, C) == (w ? 1 : 2), name, ": no one-launch form for ", N,
+              " maps of ", H, "x", W, "x", CIN, " -> ", C, " channels");
+  const c10::DeviceGuard g(x.device());
+  auto y = w ? at::empty({N, (H + 1) / 2, (W + 1) / 2, C}, x.options()) : at::empty_like(x);
+  sa::conv::stage_bf16_fwd_launch(x.data_ptr(), w ? w->data_ptr<float>() : nullptr,
+                                  w ? b->data_ptr<float>() : nullptr, wb, y.data_ptr(),
+                                  static_cast<int>(N), static_cast<int>(H),
+                                  static_cast<int>(W), static_cast<int>(CIN),
+                                  static_cast<int>(C), static_cast<int>(pb_h),
+                                  static_cast<int>(pb_w), last, stream());
+  const hipError_t e = hipGetLastError();
+  TORCH_CHECK(e == hipSuccess, name, ": launch failed: ", hipGetErrorString(e));
+  return y;
+}
+
+// y = the stage's output: conv(x, w) + b -> max-pool -> two residual blocks
+// [+ final relu]; bitwise conv_pool_fwd + two res_block_fwd
+at::Tensor stage_bf16_fwd(at::Tensor x, at::Tensor w, at::Tensor b, at::Tensor w1,
+                          at::Tensor b1, at::Tensor w2, at::Tensor b2, at::Tensor w3,
+                          at::Tensor b3, at::Tensor w4, at::Tensor b4, int64_t pb_h,
+                          int64_t pb_w, bool last) {
+  TORCH_CHECK(x.dim() == 4 && w.dim() == 4, "stage_bf16_fwd: x must be NHWC, w HWIO");
+  const int64_t CIN = x.size(3), COUT = w.size(3);
+  TORCH_CHECK(supported(CIN) && COUT == 32, "stage_bf16_fwd: channels must be 16/32 -> 32");
+  check_act(x, "x", CIN);
+  check_w(w, b, CIN, COUT);
+  const at::Tensor* blk[8] = {&w1, &b1, &w2, &b2, &w3, &b3, &w4, &b4};
+  return stage_launch(x, &w, &b, blk, COUT, pb_h, pb_w, last, "stage_bf16_fwd");
+}
+
+// y = two residual blocks [+ final relu] of a pooled 16-channel map
+at::Tensor stage_tail_bf16_fwd(at::Tensor x, at::Tensor w1, at::Tensor b1, at::Tensor w2,
+                               at::Tensor b2, at::Tensor w3, at::Tensor b3, at::Tensor w4,
+                               at::Tensor b4, bool last) {
+  TORCH_CHECK(x.dim() == 4 && x.size(3) == 16, "stage_tail_bf16_fwd: x must be NHWC, C = 16");
+  check_act(x, "x", 16);
+  const at::Tensor* blk[8] = {&w1, &b1, &w2, &b2, &w3, &b3, &w4, &b4};
+  return stage_launch(x, nullptr, nullptr, blk, 16, 0, 0, last, "stage_tail_bf16_fwd");
+}
+
 // dx = [skip +] dgrad(dy) * (act > 0); dW += relu?(act)^T dy; db += sum dy
 at::Tensor res_conv_bwd(at::Tensor dy, at::Tensor act, c10::optional<at::Tensor> skip,
                         at::Tensor w, at::Tensor dw, at::Tensor db, bool relu_act) {
@@ -281,6 +346,21 @@ void register_conv_ops(pybind11::module& m) {
   // 1 where shallow_bf16_fwd takes N uint8 frames of [H, W, C], else 0
   m.def("shallow_bf16_form",
         [](int N, int H, int W, int C) { return sa::conv::shallow_bf16_form(N, H, W, C); });
+  m.def("stage_bf16_fwd", &stage_bf16_fwd, pybind11::arg("x"), pybind11::arg("w"),
+        pybind11::arg("b"), pybind11::arg("w1"), pybind11::arg("b1"), pybind11::arg("w2"),
+        pybind11::arg("b2"), pybind11::arg("w3"), pybind11::arg("b3"), pybind11::arg("w4"),
+        pybind11::arg("b4"), pybind11::arg("pb_h"), pybind11::arg("pb_w"),
+        pybind11::arg("last"));
+  m.def("stage_tail_bf16_fwd", &stage_tail_bf16_fwd, pybind11::arg("x"),
+        pybind11::arg("w1"), pybind11::arg("b1"), pybind11::arg("w2"), pybind11::arg("b2"),
+        pybind11::arg("w3"), pybind11::arg("b3"), pybind11::arg("w4"), pybind11::arg("b4"),
+        pybind11::arg("last"));
+  // 0, 1 (stage: [frames,H,W,CIN] input, CIN -> COUT = 32) or 2 (tail: a pooled
+  // [frames,H,W,16] map, CIN == COUT == 16); host arithmetic only
+  m.def("stage_bf16_form", [](int frames, int H, int W, int CIN, int COUT) {
+          return sa::conv::stage_bf16_form(frames, H, W, CIN, COUT);
+        }, pybind11::arg("frames"), pybind11::arg("H"), pybind11::arg("W"),
+        pybind11::arg("CIN"), pybind11::arg("COUT"));
   // read-only record of a family's last launch ("" = the most recent one)
   m.def("conv_launch_info", [](const std::string& family) {
           const sa::conv::LaunchInfo i = sa::conv::launch_info(family.c_str());

@@ -67,6 +67,23 @@ int shallow_bf16_form(int N, int H, int W, int C);
 int shallow_bf16_grid_max();
 void shallow_bf16_note(int grid, int grid_max, int ntiles);
 
+// One-launch stages of the bf16 deep torso's no-grad forward
+// (stage_fwd_kernel), one workgroup per image with the stage's maps in LDS;
+// bitwise conv_pool_fwd + two res_block_fwd.  stage_bf16_form: 1 ("stage":
+// x is the stage's [N,H,W,CIN] input, CIN = 16 or 32 -> COUT = 32; head conv
+// w/b, max-pool, both blocks), 2 ("tail", CIN == COUT == 16: x is a pooled
+// [N,H,W,16] map; both blocks; w/b unused) or 0 where the stage does not fit
+// (channels, 1 <= N <= 512, the kernel's LDS against 160 KB).  Host only.
+// wb: {w1, b1, w2, b2} of block 0 then block 1.  y: [N,Hm,Wm,COUT] (the
+// pooled size for form 1, H x W for form 2); last: final ReLU.  Throws where
+// the form is 0.  Reports family "stage_bf16" (grid = min(N, grid_max),
+// ntiles = N) to launch_info; conv_tune("stage_bf16_grid", g) caps the grid.
+int stage_bf16_form(int N, int H, int W, int CIN, int COUT);
+void stage_bf16_fwd_launch(const void* x, const float* w, const float* b,
+                           const float* const wb[8], void* y, int N, int H, int W,
+                           int CIN, int COUT, int pb_h, int pb_w, bool last,
+                           hipStream_t s);
+
 // Read-only record of the last launch of a launcher family (host side; the
 // tests assert from it that the path they mean to test actually ran).
 struct LaunchInfo {

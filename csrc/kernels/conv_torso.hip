@@ -13,6 +13,9 @@
 //   pool_conv_bwd   : dY gathered from (dP, argmax) straight into LDS (never
 //                     materialised), then dgrad + wgrad + bias grad.
 //   conv1_pool_bwd  : the same for the uint8 first layer (wgrad only).
+//   stage_fwd       : actor inference only: a whole stage of one image per
+//                     workgroup with its maps in LDS (conv_pool_fwd's bands,
+//                     then both residual blocks), or the two blocks alone.
 //
 // Tiling: a workgroup (4 waves) owns R full-width rows of one image; pixels of
 // the tile are linearised and processed in 16-pixel MFMA groups (a group may
@@ -211,11 +214,24 @@ __device__ __forceinline__ void bias_regs(const float* __restrict__ bias,
     for (int i = 0; i < 4; ++i) breg[h][i] = scratch[16 * h + 4 * (lane_id() >> 4) + i];
 }
 
+// ReLU on 8 packed bf16 as one signed 16-bit max per pair (a set sign bit
+// gives 0: the same bits as relu8).
+typedef short s8 __attribute__((ext_vector_type(8)));
+template <bool RELU>
+__device__ __forceinline__ bf8 relu_in(bf8 v) {
+  if constexpr (RELU)
+    return __builtin_bit_cast(
+        bf8, __builtin_elementwise_max(__builtin_bit_cast(s8, v), s8(0)));
+  else
+    return v;
+}
+
 // Per-wave implicit GEMM over the tile (FwdChunks). x_s: halo tile
 // [rows][Wt+2][CIN]; output pixel q=(qr,qc) reads x_s[(qr+ky)*(Wt+2)+qc+kx].
 // epi(q, co0, v[4], slot) is called for every valid (pixel, 4-channel slice);
 // slot = the group's index in this wave's list (compile-time after unrolling).
-template <int CIN, int COUT, typename Epi>
+// RELU_IN: ReLU on the pixels as they are read (x_s keeps the raw values).
+template <int CIN, int COUT, bool RELU_IN = false, typename Epi>
 __device__ __forceinline__ void conv_tile_fwd(const bf16_t* x_s,
                                               const bf16_t* w_s, int Wt,
                                               int npix, Epi epi) {
@@ -269,8 +285,8 @@ __device__ __forceinline__ void conv_tile_fwd(const bf16_t* x_s,
                 w_s + (((ky * 2 + pr) * COUT + (lane & 15) + 16 * h) * 32) + 8 * (lane >> 4));
 #pragma unroll
           for (int gi = 0; gi < NC; ++gi) {
-            const bf8 b = *reinterpret_cast<const bf8*>(x_s + base[gi] + toff +
-                                                        8 * (lane >> 4));
+            const bf8 b = relu_in<RELU_IN>(*reinterpret_cast<const bf8*>(
+                x_s + base[gi] + toff + 8 * (lane >> 4)));
 #pragma unroll
             for (int h = 0; h < NH; ++h) acc[gi][h] = mfma32(a[h], b, acc[gi][h]);
           }
@@ -282,8 +298,8 @@ __device__ __forceinline__ void conv_tile_fwd(const bf16_t* x_s,
                 w_s + (tap * COUT + (lane & 15) + 16 * h) * CIN + 8 * (lane >> 4));
 #pragma unroll
           for (int gi = 0; gi < NC; ++gi) {
-            const bf8 b = *reinterpret_cast<const bf8*>(x_s + base[gi] + toff +
-                                                        8 * (lane >> 4));
+            const bf8 b = relu_in<RELU_IN>(*reinterpret_cast<const bf8*>(
+                x_s + base[gi] + toff + 8 * (lane >> 4)));
 #pragma unroll
             for (int h = 0; h < NH; ++h) acc[gi][h] = mfma32(a[h], b, acc[gi][h]);
           }
@@ -420,6 +436,61 @@ __device__ __forceinline__ void pool_tile(const bf16_t* y_s, int W, int Wo,
       lo[k] = 0x0F0F0F0Fu - (a | (b << 16));
     }
     *reinterpret_cast<uint2*>(argmax + o) = make_uint2(lo[0], lo[1]);
+  }
+}
+
+// pool_tile's window max and value unpacking as functions, for
+// pool_tile_img (pool_tile keeps its own copy: calling these there changed
+// the pool kernels' instruction schedule).  best[c] = max over the 9 taps of
+// key32 for the 8 channels at `base` (the window's first pixel in the padded
+// key image).
+template <int COUT>
+__device__ __forceinline__ void pool_window(const bf16_t* base, int Wt, int best[8]) {
+#pragma unroll
+  for (int dy = 0; dy < 3; ++dy) {
+#pragma unroll
+    for (int dx = 0; dx < 3; ++dx) {
+      const uint4 v = *reinterpret_cast<const uint4*>(base + (dy * Wt + dx) * COUT);
+      const uint32_t u[4] = {v.x, v.y, v.z, v.w};
+      const uint32_t K = 15 - (dy * 3 + dx);
+#pragma unroll
+      for (int c = 0; c < 8; ++c) {
+        const int key = static_cast<int>((c & 1) ? ((u[c >> 1] & 0xFFFF0000u) | K)
+                                                 : ((u[c >> 1] << 16) | K));
+        best[c] = (dy | dx) ? max(best[c], key) : key;
+      }
+    }
+  }
+}
+// Eight pooled bf16 from the high halves of best[] (two channels per v_perm).
+__device__ __forceinline__ uint4 pool_values(const int best[8]) {
+  uint32_t pv[4];
+#pragma unroll
+  for (int k = 0; k < 4; ++k)  // high halves of best[2k], best[2k+1]
+    pv[k] = bf2_to_ord(__builtin_amdgcn_perm(static_cast<uint32_t>(best[2 * k + 1]),
+                                             static_cast<uint32_t>(best[2 * k]),
+                                             0x07060302u));
+  return make_uint4(pv[0], pv[1], pv[2], pv[3]);
+}
+
+// pool_tile for a pooled map kept in LDS: pooled rows [i0, i0 + Rpv) go into
+// the interior of the halo image img ([Hp + 2][pitch RPo][COUT]); no argmax.
+template <int COUT>
+__device__ __forceinline__ void pool_tile_img(const bf16_t* y_s, int W, int Wo,
+                                              int pb_w, int i0, int Rpv,
+                                              bf16_t* img, int RPo) {
+  constexpr int CH = COUT / 8;
+  const int Wt = W + 2;
+  const int total = Rpv * Wo * CH;
+  for (int e = threadIdx.x; e < total; e += blockDim.x) {
+    const int part = e % CH;
+    const int pj = (e / CH) % Wo;
+    const int pi = e / (CH * Wo);
+    const bf16_t* base = y_s + ((2 * pi) * Wt + 2 * pj - pb_w) * COUT + COUT + part * 8;
+    int best[8];
+    pool_window<COUT>(base, Wt, best);
+    *reinterpret_cast<uint4*>(img + (i0 + pi + 1) * RPo + (pj + 1) * COUT + part * 8) =
+        pool_values(best);
   }
 }
 
@@ -1081,6 +1152,187 @@ __global__ __launch_bounds__(kThreads) void conv_pool_fwd_kernel(
   }
 }
 
+// ---- one-launch stages (actor inference, no backward) ----
+// LDS arithmetic shared by stage_fwd_kernel, its launcher and
+// stage_bf16_form.  A whole Hm x Wm map is a halo image [Hm + 2][pitch][C]
+// plus the pad pixel the paired taps read.
+__host__ __device__ constexpr int img_elems(int C, int Hm, int Wm) {
+  return (Hm + 2) * row_pitch(C, Wm) + C;
+}
+// Rows per conv_tile_fwd call on a whole-map image: the most whose groups
+// stay within kMaxTilePx (an even count for the 2-row groups of C = 32).
+__host__ __device__ constexpr int stage_band_rows(int C, int Wm) {
+  return C == 32 ? 2 * ((kMaxTilePx(32) / 16) / ceil_div(Wm, 8)) : kMaxTilePx(16) / Wm;
+}
+constexpr int kStageScratch = 64 * sizeof(float);  // two convs' biases
+// Head view of the union: weights, staged input rows, order-key band.
+__host__ __device__ constexpr int stage_head_elems(int CIN, int C, int W, int Rp) {
+  return w_lds_elems(CIN, C, true) + (2 * Rp + 3) * row_pitch(CIN, W) + CIN +
+         (2 * Rp + 1) * (W + 2) * C;
+}
+// Block view of the union: two convs' weights and the t image.
+__host__ __device__ constexpr int stage_block_elems(int C, int Hm, int Wm) {
+  return 2 * w_lds_elems(C, C, true) + img_elems(C, Hm, Wm);
+}
+// head: H x W x CIN input, Rp pooled rows per band; else an H x W x C map.
+__host__ __device__ constexpr int stage_lds_bytes(bool head, int CIN, int C, int H,
+                                                  int W, int Rp) {
+  const int Hm = head ? (H + 1) / 2 : H, Wm = head ? (W + 1) / 2 : W;
+  int u = stage_block_elems(C, Hm, Wm);
+  if (head && stage_head_elems(CIN, C, W, Rp) > u) u = stage_head_elems(CIN, C, W, Rp);
+  return kStageScratch + (img_elems(C, Hm, Wm) + u) * static_cast<int>(sizeof(bf16_t));
+}
+
+__device__ __forceinline__ void zero_lds(bf16_t* p, int elems) {
+  for (int e = threadIdx.x; e < elems / 8; e += kThreads)
+    reinterpret_cast<uint4*>(p)[e] = make_uint4(0, 0, 0, 0);
+}
+
+// A whole torso stage of one image per workgroup, its maps kept in LDS:
+//   HEAD  ("stage"): conv3x3(CIN->C)+b -> maxpool 3x3/2 (conv_pool_fwd's band
+//         loop on this image; the pooled rows go into the LDS image x),
+//   !HEAD ("tail") : the pooled H x W x C map is loaded from HBM into x,
+// then both residual blocks on LDS:
+//   t = relu(conv1(relu(x)) + b1) into the LDS image t,
+//   y = conv2(t) + b2 + x in place over x (the lane that writes a pixel read
+//   its skip value); the second block's y goes to HBM [+ final relu].
+// x keeps the raw values (the skip needs them), so conv1 applies its input
+// ReLU as it reads.  Every value is rounded to bf16 where conv_pool_fwd and
+// res_block_fwd round it, and conv_tile_fwd fixes a pixel's accumulation
+// order, so the result is bitwise theirs.  The head's weights, staged rows
+// and key band share LDS with the blocks' weights and t.
+template <int CIN, int C, bool HEAD, int HC, int WC, int RC>
+__global__ __launch_bounds__(kThreads) void stage_fwd_kernel(
+    const bf16_t* __restrict__ x, const float* __restrict__ w,
+    const float* __restrict__ bias, const float* __restrict__ w1,
+    const float* __restrict__ b1, const float* __restrict__ w2,
+    const float* __restrict__ b2, const float* __restrict__ w3,
+    const float* __restrict__ b3, const float* __restrict__ w4,
+    const float* __restrict__ b4, bf16_t* __restrict__ y, int N, int H_, int W_,
+    int Rp_, int pb_h, int pb_w, int last, int xcd) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int H = HC ? HC : H_, W = WC ? WC : W_, Rp = RC ? RC : Rp_;
+  const int Hm = HEAD ? (H + 1) / 2 : H, Wm = HEAD ? (W + 1) / 2 : W;
+  const int RP = row_pitch(C, Wm);
+  const int Rb = stage_band_rows(C, Wm);
+  float* scratch = reinterpret_cast<float*>(smem);
+  bf16_t* x_img = reinterpret_cast<bf16_t*>(smem + kStageScratch);
+  bf16_t* wa_s = x_img + img_elems(C, Hm, Wm);
+  bf16_t* wb_s = wa_s + w_lds_elems(C, C, true);
+  bf16_t* t_img = wb_s + w_lds_elems(C, C, true);
+  // the zero ring and pad pixel of x stay for the whole kernel (pooling and
+  // the epilogues write interior pixels only); t's too where no head
+  // overwrites them
+  zero_lds(x_img, img_elems(C, Hm, Wm));
+  if (!HEAD) zero_lds(t_img, img_elems(C, Hm, Wm));
+  const TileIter it(N, xcd);
+  for (int n = it.first; it.valid(n); n = it.next(n)) {
+    __syncthreads();  // the previous image's last reads; the zeroing above
+    if constexpr (HEAD) {
+      bf16_t* wh_s = wa_s;
+      bf16_t* xs_s = wh_s + w_lds_elems(CIN, C, true);
+      bf16_t* y_s = xs_s + (2 * Rp + 3) * row_pitch(CIN, W) + CIN;  // + pad pixel
+      load_weights4<CIN, C, true>(w, wh_s);
+      float breg[C / 16][4];
+      bias_regs<C>(bias, scratch, breg);
+      init_pool_pads<C>(y_s, 2 * Rp + 1, W);
+      RowStager<CIN, NREG> sx;
+      auto issue = [&](int i0) {
+        sx.issue(x, n, H, W, 2 * i0 - pb_h - 1, 2 * min(Rp, Hm - i0) + 3);
+      };
+      issue(0);
+      for (int i0 = 0; i0 < Hm; i0 += Rp) {
+        const int Rpv = min(Rp, Hm - i0);
+        const int cr0 = 2 * i0 - pb_h;
+        const int Rc = 2 * Rpv + 1;
+        __syncthreads();
+        sx.template commit<false, true>(xs_s, W);
+        __syncthreads();
+        // unconditional (no next band: re-issue this one, unused)
+        issue(i0 + Rp < Hm ? i0 + Rp : i0);
+        conv_tile_fwd<CIN, C>(xs_s, wh_s, W, Rc * W, [&](int q, int co0, float v[4], int) {
+#pragma unroll
+          for (int i = 0; i < 4; ++i) v[i] += breg[co0 >> 4][i];
+          const int qr = q / W;
+          store4_ord_in(y_s + (q + 2 * qr + 1) * C + co0, v,
+                        static_cast<unsigned>(cr0 + qr) < static_cast<unsigned>(H));
+        });
+        __syncthreads();
+        pool_tile_img<C>(y_s, W, Wm, pb_w, i0, Rpv, x_img, RP);
+      }
+      __syncthreads();  // x complete; the head's LDS is free for the blocks
+      zero_lds(t_img, img_elems(C, Hm, Wm));
+    } else {
+      constexpr int CH = C / 8;
+      const int rc = Wm * CH;
+      const bf16_t* src = x + static_cast<int64_t>(n) * Hm * Wm * C;
+      for (int e = threadIdx.x; e < Hm * rc; e += kThreads) {
+        const int r = e / rc, rem = e - r * rc;
+        const int px = rem / CH, part = rem - px * CH;
+        *reinterpret_cast<uint4*>(x_img + (r + 1) * RP + (px + 1) * C + part * 8) =
+            *reinterpret_cast<const uint4*>(src + static_cast<int64_t>(e) * 8);
+      }
+    }
+    bf16_t* yn = y + static_cast<int64_t>(n) * Hm * Wm * C;
+#pragma unroll 1
+    for (int blk = 0; blk < 2; ++blk) {
+      load_weights4<C, C, true>(blk ? w3 : w1, wa_s);
+      load_weights4<C, C, true>(blk ? w4 : w2, wb_s);
+      {
+        const float* ba = blk ? b3 : b1;
+        const float* bb = blk ? b4 : b2;
+        for (int e = threadIdx.x; e < 2 * C; e += kThreads)
+          scratch[e] = e < C ? ba[e] : bb[e - C];
+      }
+      __syncthreads();
+      float bq1[C / 16][4], bq2[C / 16][4];
+#pragma unroll
+      for (int h = 0; h < C / 16; ++h)
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          bq1[h][i] = scratch[16 * h + 4 * (lane_id() >> 4) + i];
+          bq2[h][i] = scratch[C + 16 * h + 4 * (lane_id() >> 4) + i];
+        }
+      // row bands of at most kMaxTilePx pixels; no barrier between them: conv1
+      // only reads x and writes t, conv2 only reads t (and its own x pixels)
+      for (int r0 = 0; r0 < Hm; r0 += Rb) {
+        const int Rv = min(Rb, Hm - r0);
+        conv_tile_fwd<C, C, true>(x_img + r0 * RP, wa_s, Wm, Rv * Wm,
+                                  [&](int q, int co0, float v[4], int) {
+          const int qr = q / Wm, qc = q - qr * Wm;
+#pragma unroll
+          for (int i = 0; i < 4; ++i) v[i] = fmaxf(v[i] + bq1[co0 >> 4][i], 0.f);
+          store4_pk(t_img + (r0 + qr + 1) * RP + (qc + 1) * C + co0, v);
+        });
+      }
+      __syncthreads();
+      for (int r0 = 0; r0 < Hm; r0 += Rb) {
+        const int Rv = min(Rb, Hm - r0);
+        conv_tile_fwd<C, C>(t_img + r0 * RP, wb_s, Wm, Rv * Wm,
+                            [&](int q, int co0, float v[4], int) {
+          const int qr = q / Wm, qc = q - qr * Wm;
+          bf16_t* xp = x_img + (r0 + qr + 1) * RP + (qc + 1) * C + co0;
+          float r[4];
+          load4(xp, r);
+#pragma unroll
+          for (int i = 0; i < 4; ++i) {
+            v[i] += bq2[co0 >> 4][i];  // same rounding order as res_block_fwd
+            v[i] += r[i];
+          }
+          if (blk == 0) {
+            store4_pk(xp, v);
+          } else {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) v[i] = last ? fmaxf(v[i], 0.f) : v[i];
+            store4_pk(yn + (static_cast<int64_t>(r0 + qr) * Wm + qc) * C + co0, v);
+          }
+        });
+      }
+      __syncthreads();  // y of block 0 complete; weights and scratch are free
+    }
+  }
+}
+
 // First layer: the uint8 frame tile is staged as bf16x4 pixels (raw byte
 // values are exact in bf16; 1/255 is folded into the weights).  With 4 values
 // per pixel, one 16x16x16 MFMA covers a whole kernel row (kx = 0..2 plus a
@@ -1685,6 +1937,7 @@ struct ConvTune {
   int ablate = 0;         // timing-only, -DSA_CONV_ABLATE builds: skip phases
   int deterministic = 0;  // wgrad: per-workgroup slots + fixed-order reduce
   int shallow_bf16_grid = 0;  // conv_shallow_bf16.hip: max workgroups (0 = no cap)
+  int stage_bf16_grid = 0;    // stage_fwd_kernel: max workgroups (0 = no cap)
 };
 constexpr ConvTune kDef{};
 static ConvTune g_tune;
@@ -1699,7 +1952,8 @@ int conv_tune_set(const char* key, int value) {
       {"px_conv1_bwd", &g_tune.px_conv1_bwd},
       {"specialize", &g_tune.specialize}, {"ablate", &g_tune.ablate},
       {"deterministic", &g_tune.deterministic},
-      {"shallow_bf16_grid", &g_tune.shallow_bf16_grid}};
+      {"shallow_bf16_grid", &g_tune.shallow_bf16_grid},
+      {"stage_bf16_grid", &g_tune.stage_bf16_grid}};
   for (auto& e : table) {
     if (std::strcmp(e.k, key) == 0) {
       const int old = *e.v;
@@ -1758,10 +2012,12 @@ bool with_geo(int H, int W, int R, F&& f) {
 
 // Launch records, one per launcher family (launch_info()).
 enum Family { kResConvFwd, kResBlockFwd, kConvPoolFwd, kConv1PoolFwd,
-              kResConvBwd, kPoolConvBwd, kConv1PoolBwd, kShallowBf16, kFamilies };
+              kResConvBwd, kPoolConvBwd, kConv1PoolBwd, kShallowBf16, kStageBf16,
+              kFamilies };
 constexpr const char* kFamilyName[kFamilies] = {
     "res_conv_fwd", "res_block_fwd", "conv_pool_fwd", "conv1_pool_fwd",
-    "res_conv_bwd", "pool_conv_bwd", "conv1_pool_bwd", "shallow_bf16"};
+    "res_conv_bwd", "pool_conv_bwd", "conv1_pool_bwd", "shallow_bf16",
+    "stage_bf16"};
 LaunchInfo g_launch[kFamilies] = {};
 int g_last_family = -1;
 void note_launch(Family f, int grid, int grid_max, int ntiles, int rows,
@@ -1788,6 +2044,9 @@ struct RowsPoolFwd {
 };
 struct RowsConv1Fwd {
   static constexpr int rows(int H, int W) { return rows_conv1_fwd(H, W, kDef.px_conv1_fwd); }
+};
+struct RowsStageTail {  // stage_fwd_kernel's tail form has no head bands
+  static constexpr int rows(int, int) { return 0; }
 };
 template <int CIN, int COUT>
 struct RowsPoolBwd {
@@ -1975,6 +2234,63 @@ void conv1_pool_fwd_launch(const uint8_t* x, const float* w, const float* b,
                        argmax, N, H, W, Rp, pb_h, pb_w, xcd);
   });
   note_launch(kConv1PoolFwd, grid, grid_max, ntiles, Rp, spec);
+}
+
+// 0: no one-launch form; 1 "stage": [N,H,W,CIN] input, CIN -> COUT = 32 head,
+// pool and both blocks; 2 "tail" (CIN == COUT == 16): both blocks of a pooled
+// [N,H,W,16] map.  Host arithmetic only: channels, 1-512 frames, the head's
+// band staging and the kernel's LDS (stage_lds_bytes) against 160 KB.  The
+// head's bands use the default px_pool_fwd whatever conv_tune says.
+int stage_bf16_form(int N, int H, int W, int CIN, int COUT) {
+  if (N < 1 || N > 512 || H < 1 || W < 1 || H > 4096 || W > 4096) return 0;
+  const bool tail = CIN == 16 && COUT == 16;
+  if (!tail && !((CIN == 16 || CIN == 32) && COUT == 32)) return 0;
+  if (stage_band_rows(COUT, tail ? W : (W + 1) / 2) < 1) return 0;
+  int Rp = 0;
+  if (!tail) {
+    Rp = rows_pool_fwd(H, W, CIN, kDef.px_pool_fwd);
+    if ((2 * Rp + 3) * W * CIN / 8 > NREG * kThreads ||
+        tile_groups(CIN, 2 * Rp + 1, W) > kMaxTilePx(CIN) / 16)
+      return 0;
+  }
+  if (stage_lds_bytes(!tail, CIN, COUT, H, W, Rp) > 160 * 1024) return 0;
+  return tail ? 2 : 1;
+}
+
+void stage_bf16_fwd_launch(const void* x, const float* w, const float* b,
+                           const float* const wb[8], void* y, int N, int H, int W,
+                           int CIN, int COUT, int pb_h, int pb_w, bool last,
+                           hipStream_t s) {
+  const int form = stage_bf16_form(N, H, W, CIN, COUT);
+  if (!form)
+    throw std::invalid_argument("stage_bf16_fwd: no one-launch form for this stage");
+  const bool head = form == 1;
+  const int Rp = head ? rows_pool_fwd(H, W, CIN, kDef.px_pool_fwd) : 0;
+  const size_t smem = stage_lds_bytes(head, CIN, COUT, H, W, Rp);
+  int grid_max = 0;
+  grid_for(N, smem, g_tune.cap_fwd, &grid_max);
+  if (g_tune.stage_bf16_grid > 0 && g_tune.stage_bf16_grid < grid_max)
+    grid_max = g_tune.stage_bf16_grid;
+  const int grid = N < grid_max ? N : grid_max;
+  auto X = static_cast<const bf16_t*>(x);
+  auto Y = static_cast<bf16_t*>(y);
+  auto go = [&](auto kernel) {
+    set_smem(kernel, smem);
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(kThreads), smem, s, X, w, b, wb[0],
+                       wb[1], wb[2], wb[3], wb[4], wb[5], wb[6], wb[7], Y, N, H, W, Rp,
+                       pb_h, pb_w, last ? 1 : 0, g_tune.xcd);
+  };
+  bool spec = false;
+#define SA_ST(CI, CO, HD, RF, STG)                                             \
+  spec = with_geo<STG, RF>(H, W, Rp, [&](auto h, auto ww, auto r) {            \
+    go(stage_fwd_kernel<CI, CO, HD, decltype(h)::value, decltype(ww)::value,   \
+                        decltype(r)::value>);                                  \
+  })
+  if (!head) SA_ST(16, 16, false, RowsStageTail, kStage1);
+  else if (CIN == 16) SA_ST(16, 32, true, RowsPoolFwd<16>, kStage1);
+  else SA_ST(32, 32, true, RowsPoolFwd<32>, kStage2);
+#undef SA_ST
+  note_launch(kStageBf16, grid, grid_max, N, Rp, spec);
 }
 
 // Deterministic mode: floats of the slot workspace a wgrad launch needs (0

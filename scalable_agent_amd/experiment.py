@@ -154,7 +154,8 @@ def _make_agent(flags, num_actions, frame_shape, device, seed, dtype=None):
                num_value_heads=num_value_heads(flags),
                pipeline_chunks=getattr(flags, 'pipeline_chunks', 1),
                actor_core=getattr(flags, 'actor_core', 'ops'),
-               torso_blocks=getattr(flags, 'torso_blocks', 'ops'))
+               torso_blocks=getattr(flags, 'torso_blocks', 'ops'),
+               torso_stages=getattr(flags, 'torso_stages', 'ops'))
 
 
 def _log_torso_blocks(flags, model):
@@ -220,6 +221,37 @@ def _log_torso_blocks(flags, model):
     why = 'bf16 inference already runs one kernel per block'
   log.info('actor inference torso blocks: %s (--torso_blocks=%s does not '
            'apply: %s)', used, asked, why)
+
+
+def _log_torso_stages(flags, model):
+  """Which form the inference model's bf16 deep-torso stages run
+  (--torso_stages)."""
+  asked = getattr(flags, 'torso_stages', 'ops')
+  used = model.torso_stages
+  agent = model.agent
+  if asked != 'fused':
+    log.info('actor inference torso stages: ops')
+    return
+  frame = 'x'.join(str(d) for d in agent.frame_shape)
+  if used is not None and any(used):
+    names = {'stage': 'stage (head, max-pool and both blocks in one launch)',
+             'tail': 'tail (both blocks in one launch)',
+             None: 'ops (declines)'}
+    log.info('actor inference torso stages: fused on %s frames: %s', frame,
+             ', '.join('stage %d %s' % (s, names[f]) for s, f in enumerate(used)))
+    return
+  if getattr(agent, 'backend', 'torch') != 'hip' or model.device.type != 'cuda':
+    why = 'the torch backend has no stage kernel'
+  elif agent.torso_kind != 'deep':
+    why = 'the %s torso has no stages' % agent.torso_kind
+  elif str(agent.compute_dtype) != 'torch.bfloat16':
+    why = 'the one-launch stages are bf16 only (see --torso_blocks for fp32)'
+  elif used is None:
+    why = 'the bf16 torso kernels do not take %s frames' % frame
+  else:
+    why = 'no stage of %s frames fits a workgroup' % frame
+  log.info('actor inference torso stages: ops (--torso_stages=fused does not '
+           'apply: %s)', why)
 
 
 def _log_torso_precision(model):
@@ -694,6 +726,7 @@ def train(flags):
         if lane == 0:
           _log_actor_core(flags, lane_model)
           _log_torso_blocks(flags, lane_model)
+          _log_torso_stages(flags, lane_model)
           _log_torso_precision(lane_model)
         servers.append(BoardServer(lane_model, lane_board,
                                    gather_us=flags.inference_gather_us,
@@ -718,6 +751,7 @@ def train(flags):
                                          seed=flags.seed + 17 * rank)
     _log_actor_core(flags, model)
     _log_torso_blocks(flags, model)
+    _log_torso_stages(flags, model)
     _log_torso_precision(model)
     model.publish(learner.flat.params)
     infer = inference_lib.make_batched_infer(

@@ -153,6 +153,19 @@ def build_parser() -> argparse.ArgumentParser:
                       'give bitwise the same features.  bf16 inference fuses '
                       'its blocks already, and bf16 and the torch backend run '
                       'as with ops.')
+  p.add_argument('--torso_stages', default='ops', choices=['ops', 'fused'],
+                 help='One-launch stages of the bf16 HIP deep torso in actor '
+                      'inference (no autograd, at most 512 frames per launch): '
+                      'ops = a head launch and one launch per residual block; '
+                      'fused = stages 1 and 2 (head conv, max-pool and both '
+                      'blocks) in ONE kernel each and the two blocks of stage 0 '
+                      'in ONE kernel, one workgroup per frame with the '
+                      'stage\'s maps in LDS: nine torso launches become four '
+                      'on 72x96 and 84x84 frames (72x128: stage 0 keeps its '
+                      'block launches, its maps exceed the LDS).  Bitwise the '
+                      'same features.  fp32 agents (see --torso_blocks), the '
+                      'shallow torso, the learner and the torch backend run as '
+                      'with ops; the start-up log names what runs.')
   p.add_argument('--inference_device', default='auto',
                  help='Device of the actor-inference model: auto = the '
                       'learner device; e.g. cuda:1 or cpu.')

@@ -165,6 +165,15 @@ class InferenceModel(object):
     form = getattr(self.agent, 'torso_stage_form', None)
     return 'stage' if form is not None and form(cuda) else 'fused'
 
+  @property
+  def torso_stages(self):
+    """What Agent(torso_stages='fused') runs per stage of this model's bf16
+    deep torso: a 3-tuple of 'stage', 'tail' or None (Agent.torso_stages_form);
+    None where it was not asked for or does not apply (the torso runs as with
+    'ops')."""
+    form = getattr(self.agent, 'torso_stages_form', None)
+    return None if form is None else form(self.device.type == 'cuda')
+
   @torch.no_grad()
   def step_device(self, last_action, reward, done, frame, instr_ids,
                   instr_len, c, h, has_instr, epilogue=None):

@@ -123,8 +123,15 @@ class Agent(nn.Module):
   def __init__(self, num_actions, torso='shallow', frame_shape=(72, 96, 3),
                seed=None, backend='torch', compute_dtype=torch.float32,
                num_value_heads=1, pipeline_chunks=1, actor_core='ops',
-               torso_blocks='ops'):
+               torso_blocks='ops', torso_stages='ops'):
     super().__init__()
+    # 'fused': a no-grad forward of the bf16 HIP deep torso on a board's
+    # worth of frames runs each stage whose maps fit a workgroup's LDS as ONE
+    # kernel (ops/conv.py torso_forward_stages) where it applies
+    # (torso_stages_form); 'ops': a head launch and one launch per block
+    if torso_stages not in ('ops', 'fused'):
+      raise ValueError('unknown torso_stages %r' % (torso_stages,))
+    self.torso_stages = torso_stages
     # 'fused': a no-grad forward of the fp32 HIP deep torso on a board's
     # worth of frames runs each residual block as ONE kernel
     # (ops/conv_f32.py _DeepTorsoF32Infer) where it applies
@@ -250,6 +257,11 @@ class Agent(nn.Module):
     if self.backend == 'hip' and frames.is_cuda:
       from .. import ops
       if _bf16_torso_ready(self):
+        if (self.torso_stages == 'fused' and not torch.is_grad_enabled() and
+            frames.shape[0] <= ops.conv.FUSED_BLOCK_MAX_FRAMES and
+            any(ops.conv.deep_stage_bf16_form(frames.shape[1:],
+                                              frames.shape[0]))):
+          return ops.conv.torso_forward_stages(self, frames)
         return ops.torso_forward(self, frames)
       # actor inference of a bf16 shallow agent: the whole conv torso in one
       # bf16 MFMA launch (bf16 features: the bf16 FC GEMM and core follow);
@@ -592,6 +604,19 @@ class Agent(nn.Module):
     return (self.torso_blocks in ('fused', 'stage', 'heads', 'whole') and
             self.backend == 'hip' and cuda and self.torso_kind == 'deep' and
             not _bf16_torso_ready(self))
+
+  def torso_stages_form(self, cuda=True):
+    """What `torso_stages='fused'` runs per stage for a no-grad forward of
+    CUDA frames of this agent's shape: a 3-tuple of 'stage' (head, max-pool
+    and both blocks in one launch), 'tail' (both blocks in one launch) or
+    None (that stage's launches as with 'ops'); None: not asked for, or it
+    cannot apply (it needs the HIP backend, bf16 compute and the deep torso on
+    frames the bf16 kernels take)."""
+    if (self.torso_stages != 'fused' or self.backend != 'hip' or not cuda or
+        self.torso_kind != 'deep' or not _bf16_torso_ready(self)):
+      return None
+    from ..ops import conv
+    return conv.deep_stage_bf16_form(self.frame_shape)
 
   def torso_stage_form(self, cuda=True):
     """What `torso_blocks='stage'` (or `'heads'`, which includes it) runs for

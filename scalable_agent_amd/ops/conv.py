@@ -10,6 +10,11 @@ one pass that gathers the pooled gradient through the saved argmax in LDS.
 All activations NHWC bf16; weights/biases fp32 master copies (TF HWIO); their
 gradients accumulate in fp32 directly inside the kernels.
 
+torso_forward_stages (Agent(torso_stages='fused'), no autograd) runs each
+stage whose maps fit a workgroup's LDS as ONE launch (stage_fwd_kernel:
+stage_bf16_fwd, or stage_tail_bf16_fwd after conv1_pool_fwd), bitwise the
+launches above.
+
 The SHALLOW torso has one bf16 kernel, for actor inference only
 (csrc/kernels/conv_shallow_bf16.hip, torso_forward_shallow_bf16): x / 255 and
 the three convs (8x8/4, 4x4/2, 3x3/2) of a no-grad forward in one launch on
@@ -190,6 +195,136 @@ def torso_forward(agent, frames):
                             frames.shape[0] <= FUSED_BLOCK_MAX_FRAMES)
         else _DeepTorso)
   return _chunked(fn, frames.contiguous(), deep_param_list(agent))
+
+
+# ---- one-launch stages of the no-grad forward (stage_fwd_kernel) ----
+# Host mirror of the launcher's arithmetic (conv_torso.hip: row_pitch,
+# tile_groups, rows_pool_fwd, stage_lds_bytes): the binding's stage_bf16_form
+# says the same (tests/test_torso_stages_flag.py).
+_STAGE_LDS_LIMIT = 160 * 1024
+_STAGE_FORMS = (None, 'stage', 'tail')
+
+
+def _row_pitch(c, w):
+  return (w + 2) * c + (16 if c == 32 else 0)
+
+
+def _tile_groups(c, rows, w):
+  if c == 32:
+    return -(-rows // 2) * -(-w // 8)
+  return -(-(rows * w) // 16)
+
+
+def _max_tile_px(c):
+  return 4 * 256 * 8 // c
+
+
+def _w_lds_elems(cin, cout):
+  return 192 * cout if cin == 16 else 9 * cin * cout
+
+
+def _rows_pool_fwd(h, w, cin, px=400):
+  hp = (h + 1) // 2
+  rp = max((px // w - 1) // 2, 1)
+  while rp > 1 and ((2 * rp + 3) * w * cin // 8 > 1024 or
+                    _tile_groups(cin, 2 * rp + 1, w) > _max_tile_px(cin) // 16):
+    rp -= 1
+  rp = min(rp, hp)
+  if 1 <= rp < hp:  # balance_rows
+    n = -(-hp // rp)
+    if 4 * (hp - (n - 1) * rp) < rp:
+      rp = -(-hp // n)
+  return rp
+
+
+def stage_bf16_lds_bytes(h, w, cin, cout):
+  """LDS bytes of the one-launch stage kernel: a [h, w, cin] stage input
+  (cin -> cout = 32 head, pool, two blocks) or, cin == cout == 16, a pooled
+  [h, w, 16] map (the two blocks)."""
+  tail = cin == cout == 16
+  hm, wm = (h, w) if tail else ((h + 1) // 2, (w + 1) // 2)
+  img = (hm + 2) * _row_pitch(cout, wm) + cout
+  union = 2 * _w_lds_elems(cout, cout) + img
+  if not tail:
+    rp = _rows_pool_fwd(h, w, cin)
+    union = max(union, _w_lds_elems(cin, cout) +
+                (2 * rp + 3) * _row_pitch(cin, w) + cin +
+                (2 * rp + 1) * (w + 2) * cout)
+  return 256 + (img + union) * 2
+
+
+def stage_bf16_form(frames, h, w, cin, cout):
+  """0, 1 (stage) or 2 (tail): the binding's stage_bf16_form in host Python."""
+  frames, h, w = int(frames), int(h), int(w)
+  if not (1 <= frames <= FUSED_BLOCK_MAX_FRAMES and 1 <= h <= 4096 and
+          1 <= w <= 4096):
+    return 0
+  tail = cin == cout == 16
+  if not tail and not (cin in (16, 32) and cout == 32):
+    return 0
+  wm = w if tail else (w + 1) // 2
+  band = 2 * (16 // -(-wm // 8)) if cout == 32 else 512 // wm
+  if band < 1:
+    return 0
+  if not tail:
+    rp = _rows_pool_fwd(h, w, cin)
+    if ((2 * rp + 3) * w * cin // 8 > 1024 or
+        _tile_groups(cin, 2 * rp + 1, w) > _max_tile_px(cin) // 16):
+      return 0
+  if stage_bf16_lds_bytes(h, w, cin, cout) > _STAGE_LDS_LIMIT:
+    return 0
+  return 2 if tail else 1
+
+
+def deep_stage_bf16_form(frame_shape, frames=1):
+  """Per stage of the deep torso on `frames` uint8 frames of [H, W, C]:
+  'stage' (head conv, max-pool and both blocks in one launch), 'tail' (stage
+  0: both blocks in one launch after conv1_pool_fwd) or None (today's
+  launches).  Host arithmetic only."""
+  if len(frame_shape) != 3:
+    return (None, None, None)
+  h, w, _ = (int(d) for d in frame_shape)
+  if h < 1 or w < 1:
+    return (None, None, None)
+  h1, w1 = (h + 1) // 2, (w + 1) // 2
+  h2, w2 = (h1 + 1) // 2, (w1 + 1) // 2
+  return (_STAGE_FORMS[stage_bf16_form(frames, h1, w1, 16, 16)],
+          _STAGE_FORMS[stage_bf16_form(frames, h1, w1, 16, 32)],
+          _STAGE_FORMS[stage_bf16_form(frames, h2, w2, 32, 32)])
+
+
+def torso_forward_stages(agent, frames):
+  """torso_forward's no-grad forward with each stage in the one-launch form
+  deep_stage_bf16_form names for it (bitwise the same features); a stage with
+  no form runs conv_pool_fwd + two res_block_fwd.  No autograd."""
+  if not supports(agent):
+    raise NotImplementedError(
+        'bf16 HIP torso: deep ResNet on 3/4-channel uint8 frames only (got %r, %r)' %
+        (agent.torso_kind, agent.frame_shape))
+  if frames.dtype != torch.uint8:
+    raise TypeError('HIP torso expects uint8 frames, got %s' % frames.dtype)
+  C = ext()
+  params = [p.detach() for p in deep_param_list(agent)]
+  forms = deep_stage_bf16_form(frames.shape[1:], frames.shape[0])
+  x = frames.contiguous()
+  for s in range(3):
+    w, b = params[10 * s], params[10 * s + 1]
+    blocks = params[10 * s + 2:10 * s + 10]
+    pb_h, pb_w = _pool_pads(x.shape[1], x.shape[2])
+    last = s == 2
+    if forms[s] == 'stage':
+      x = C.stage_bf16_fwd(x, w, b, *blocks, pb_h, pb_w, last)
+      continue
+    if s == 0:
+      x = C.conv1_pool_fwd(x, w, b, pb_h, pb_w)[0]
+    else:
+      x = C.conv_pool_fwd(x, w, b, pb_h, pb_w)[0]
+    if forms[s] == 'tail':
+      x = C.stage_tail_bf16_fwd(x, *blocks, last)
+    else:
+      x = C.res_block_fwd(x, *blocks[:4], False)[1]
+      x = C.res_block_fwd(x, *blocks[4:], last)[1]
+  return x.reshape(x.shape[0], -1)
 
 
 SHALLOW_BF16_FRAMES = ((72, 96), (84, 84), (72, 128))
