@@ -400,7 +400,7 @@ std::vector<at::Tensor> wino_conv_pool_fwd(at::Tensor x, at::Tensor w, at::Tenso
   return {y, arg};
 }
 
-// Stage-0 / stage-1 head for actor inference in one launch (conv_wino.hip
+// Stage-0 / stage-1 head for actor inference in one launch (conv_wino_infer.hip
 // wino_head_infer_kernel): x uint8 NHWC frames with 1..4 channels (w HWIO
 // [3,3,C,16] or zero-padded to [3,3,4,16]) or float32 NHWC with 16 channels
 // (w [3,3,16,32]) -> {pooled}, bitwise cf32_frames_f32 +
@@ -435,7 +435,7 @@ std::vector<at::Tensor> head_fwd(at::Tensor x, at::Tensor w, at::Tensor b) {
 }
 
 // Whole residual block (actor inference): y = conv2(relu(conv1(relu(x)) + b1))
-// + b2 + x [relu when last] in one launch (conv_wino.hip
+// + b2 + x [relu when last] in one launch (conv_wino_infer.hip
 // wino_res_block_kernel), bitwise the two cf32_conv_fwd calls; {} when the
 // shape is not covered (nothing ran; the caller runs the two convs)
 std::vector<at::Tensor> res_block_fwd(at::Tensor x, at::Tensor w1, at::Tensor b1, at::Tensor w2,
@@ -468,7 +468,7 @@ std::vector<at::Tensor> res_block_fwd(at::Tensor x, at::Tensor w1, at::Tensor b1
 }
 
 // The last stage of the deep torso (actor inference) in one launch
-// (conv_wino.hip wino_stage_tail_kernel).  head == nullptr: both residual
+// (conv_wino_infer.hip wino_stage_tail_kernel).  head == nullptr: both residual
 // blocks of x [N,H,W,32], bitwise two cf32_res_block_fwd; else x is the
 // stage's input [N,18,24,32] and the head (conv + bias + max-pool) runs in
 // the same launch, bitwise cf32_wino_conv_pool_fwd followed by the blocks.

@@ -166,7 +166,7 @@ struct WinoLaunchInfo {
 };
 WinoLaunchInfo conv_wino_launch_info(bool reset);
 bool wino_conv_launch(const ConvArgs& a, bool flip, hipStream_t s);
-// Whole residual block for actor inference (conv_wino.hip
+// Whole residual block for actor inference (conv_wino_infer.hip
 // wino_res_block_kernel), C = 16 or 32, fp32 NHWC:
 //   t = relu(conv1(relu(x)) + b1);  y = conv2(t) + b2 + x  [relu when last]
 // in one launch, t only in LDS; bitwise the two wino_conv_launch calls it
@@ -181,7 +181,7 @@ bool wino_res_block_launch(const float* x, const float* w1, const float* b1, con
                            const float* b2, float* y, int N, int H, int W, int C, bool last,
                            hipStream_t s);
 // The last stage of the deep torso for actor inference in one launch, one
-// workgroup per image (conv_wino.hip wino_stage_tail_kernel), C = 32, fp32
+// workgroup per image (conv_wino_infer.hip wino_stage_tail_kernel), C = 32, fp32
 // NHWC, w / b = {conv1a, conv2a, conv1b, conv2b}:
 //   wino_stage_tail_launch  both residual blocks of a stage whose whole map
 //                           fits in LDS beside U (9x12, 11x11, 9x16), x', t
@@ -204,7 +204,7 @@ bool wino_stage_launch(const float* x, const float* wh, const float* bh,
 // arithmetic only.
 int wino_stage_form(int N, int H, int W, int C);
 // The stage-0 / stage-1 heads of the deep torso for actor inference in one
-// launch each (conv_wino.hip wino_head_infer_kernel): conv3x3/1 SAME + bias +
+// launch each (conv_wino_infer.hip wino_head_infer_kernel): conv3x3/1 SAME + bias +
 // 3x3/2 SAME max-pool, pooled [N,H/2,W/2,Cout] only (no argmax, no scratch).
 //   is_u8   x uint8 [N,H,W,Cs], Cs 1..4, Cout 16, W in {96, 84, 128},
 //           H % 4 == 0, W * Cs % 4 == 0; w HWIO [3,3,wcin,16] with wcin == Cs

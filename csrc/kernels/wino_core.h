@@ -1,11 +1,10 @@
 // The Winograd F(2x2, 3x3) phases shared by the fp32 conv kernels of
-// conv_wino.hip, and their device utilities.  The two fused stage heads, the
-// fused residual block and the one-launch last stage are built from these
-// functions alone; the
-// forward / data-gradient kernel calls the weight transform, the stager and
-// the input / output transforms; the two fused backward kernels the weight
-// transform and the slot tables.  Where a kernel keeps text of its own, a
-// comment there says what was measured.
+// conv_wino.hip and conv_wino_infer.hip, their device utilities and the stage
+// heads' pool helpers.  The two fused stage heads and the inference kernels
+// are built from these functions alone; the forward / data-gradient kernel
+// calls the weight transform, the stager and the input / output transforms;
+// the two fused backward kernels the weight transform and the slot tables.
+// Where a kernel keeps text of its own, a comment there says what was measured.
 //
 //   Y(2x2 tile) = A^T [ sum_ci (G g_ci,co G^T) .* (B^T d_ci B) ] A
 //
@@ -79,6 +78,12 @@ __device__ __forceinline__ f4 bload(__amdgpu_buffer_rsrc_t r, uint32_t byte_off)
   return __builtin_bit_cast(f4, __builtin_amdgcn_raw_buffer_load_b128(r, byte_off, 0, 0));
 }
 constexpr int64_t kMaxBufBytes = 0xFFFFFF00ll;
+
+// x / d for 0 <= x < 2^22, 1 <= d <= 2^10 (exact: (x + 0.5) / d lies at
+// least 0.5 / d from an integer, far above the fp32 product's error)
+__device__ __forceinline__ int fdivi(int x, float rd) {
+  return static_cast<int>((static_cast<float>(x) + 0.5f) * rd);
+}
 
 // Winograd transform add / subtract, on float4 channel quads or scalars.  (A
 // packed v_pk_add_f32 form was measured in round 4 and removed: the backend
@@ -294,6 +299,115 @@ __device__ __forceinline__ void wino_prefetch(__amdgpu_buffer_rsrc_t src, const 
     stg[k] = bload(src, in ? static_cast<uint32_t>(rb + sl_x[k]) * 4u : kOOB);
   }
 }
+
+// ------------------------------- the stage heads' 3x3 / 2 SAME max-pool
+__device__ __forceinline__ void pool_take(f4& best, int (&code)[4], const f4 v, int c) {
+#pragma unroll
+  for (int q = 0; q < 4; ++q)
+    if (v[q] > best[q]) {  // strict: the first maximal tap wins
+      best[q] = v[q];
+      code[q] = c;
+    }
+}
+
+// Pool-phase lane -> (pooled column, channel quad) map of one wave (64 / CQ
+// columns x CQ quads): every 16-lane group of a ds_read_b128 (gfx950 lane
+// groups {0-3,12-15,20-27}, {4-11,16-19,28-31}, {32-35,44-47,52-59},
+// {36-43,48-51,60-63}) reads 16 distinct 16-B bank segments of the pre-pool
+// image (pixel pitch IPP floats, pooled column pj -> pixel 2 pj): each
+// segment s = (pj IPP / 2 + pq) mod 16 is taken by exactly one (pj, pq) per
+// group.  The natural map (pq = lane % CQ) put 2-4 lanes of a group on one
+// segment.
+__host__ __device__ constexpr int b128_group(int l) {
+  const int h = l & 31;
+  const int g = (h < 4 || (h >= 12 && h < 16) || (h >= 20 && h < 28)) ? 0 : 1;
+  return g + 2 * (l >> 5);
+}
+template <int CQ, int IPP>
+struct PoolLaneMap {
+  unsigned char pj[64] = {}, pq[64] = {};
+  constexpr PoolLaneMap() {
+    constexpr int NP = 64 / CQ;
+    bool used[64] = {};
+    for (int g = 0; g < 4; ++g) {
+      int next = 0;  // next lane of group g to assign
+      for (int seg = 0; seg < 16; ++seg) {
+        int pick = -1;
+        for (int c = 0; c < NP && pick < 0; ++c)
+          for (int q = 0; q < CQ && pick < 0; ++q)
+            if (!used[c * CQ + q] && (c * (IPP / 2) + q) % 16 == seg) pick = c * CQ + q;
+        while (b128_group(next) != g) ++next;
+        used[pick] = true;
+        pj[next] = static_cast<unsigned char>(pick / CQ);
+        pq[next] = static_cast<unsigned char>(pick % CQ);
+        ++next;
+      }
+    }
+  }
+};
+template <int CQ, int IPP>
+constexpr bool pool_lane_map_ok() {
+  constexpr PoolLaneMap<CQ, IPP> m{};
+  bool seen[64] = {};
+  for (int l = 0; l < 64; ++l) {
+    const int id = m.pj[l] * CQ + m.pq[l];
+    if (m.pj[l] >= 64 / CQ || seen[id]) return false;
+    seen[id] = true;
+  }
+  return true;
+}
+static_assert(pool_lane_map_ok<8, 36>() && pool_lane_map_ok<4, 20>(), "pool lane map");
+
+// LDS plan of a conv + pool over one WHOLE image per workgroup
+template <int CIN, int COUT, int H, int W>
+struct PoolImgGeo {
+  static constexpr int TY = H / 2, TX = W / 2, NTI = TY * TX;
+  static constexpr int RT = (NTI + 15) / 16 * 16;
+  static constexpr int NG = RT / 16, NS = COUT / 16, NTASK = NG * NS;
+  static constexpr int NW = 8;                       // tasks: two per wave (0..5), one (6, 7)
+  static constexpr int ROWS = H + 2, Wl = W + 2;
+  static constexpr int PP = CIN + 4, IPP = COUT + 4;
+  static constexpr int XREG = (ROWS * Wl * PP > H * W * IPP) ? ROWS * Wl * PP : H * W * IPP;
+  // only the image interior is staged (the zero border is rewritten per image)
+  static constexpr int MAXC = (H * W * (CIN / 4) + 64 * NW - 1) / (64 * NW);
+  static constexpr size_t bytes = sizeof(float) * (16 * CIN * COUT + XREG + ROWS);
+};
+
+// The 3x3 / 2 window of pooled element (pr, pc), channel quad pq, over a whole
+// pre-pool LDS image [H][W][IPP] (pad-before 0: the tap row / column past the
+// map is padding), taps in row-major order
+template <int H, int W, int IPP>
+__device__ __forceinline__ void pool_window_img(const float* img, int pr, int pc, int pq, f4& best,
+                                                int (&code)[4]) {
+#pragma unroll
+  for (int dy = 0; dy < 3; ++dy)
+#pragma unroll
+    for (int dx = 0; dx < 3; ++dx) {
+      const int y = 2 * pr + dy, x = 2 * pc + dx;
+      if (y < H && x < W)
+        pool_take(best, code, *reinterpret_cast<const f4*>(img + (y * W + x) * IPP + 4 * pq),
+                  3 * dy + dx);
+    }
+}
+
+template <typename Kern>
+void allow_lds_w(Kern k, size_t bytes) {
+  if (bytes > 64 * 1024) {
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k),
+                                             hipFuncAttributeMaxDynamicSharedMemorySize,
+                                             static_cast<int>(bytes));
+    if (e != hipSuccess) (void)hipGetLastError();  // the launch reports it
+  }
+}
+
+// While set, a Winograd launcher answers whether it would run the shape and
+// launches nothing.  Defined in conv_wino.hip; set only by a WinoProbe, which nests.
+extern thread_local bool t_wino_probe;
+struct WinoProbe {
+  const bool prev = t_wino_probe;
+  WinoProbe() { t_wino_probe = true; }
+  ~WinoProbe() { t_wino_probe = prev; }
+};
 
 }  // namespace wino
 }  // namespace cf32
