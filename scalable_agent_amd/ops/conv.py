@@ -160,6 +160,8 @@ def _deep_backward(ctx, grad_out):
   dy = grad_out.reshape(out.shape)
   if dy.dtype != torch.bfloat16 or not dy.is_contiguous():
     dy = dy.to(torch.bfloat16).contiguous()
+  else:
+    dy = dy.clone()  # grad_out belongs to autograd: never masked in place
   C.relu_mask_bf16_(dy, out)
   p_base = [0, 10, 20]
   for s in reversed(range(3)):

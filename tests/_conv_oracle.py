@@ -195,14 +195,17 @@ def scatter64(dP, code, H, W, pb_h, pb_w):
 
 # ------------------------------------------------------------------ checks
 
-def check_bound(out, ref, A, K, what):
+def check_bound(out, ref, A, K, what, extra=None):
   """|out - ref| <= 2^-8 |ref| + 9 K 2^-23 A elementwise; prints the largest
-  error / bound ratio."""
+  error / bound ratio.  `extra` (a tensor like ref) is added to the bound
+  where the caller derives a further term."""
   out = d64(out)
   assert out.shape == ref.shape, (out.shape, ref.shape)
   assert bool(torch.isfinite(out).all()), what
   err = (out - ref).abs()
   bound = REL * ref.abs() + 9 * K * ACC * A
+  if extra is not None:
+    bound = bound + extra
   ratio = float((err / bound.clamp_min(1e-300)).max())
   print('CONVERR %s ratio=%.4f' % (what, ratio))
   over = err > bound
