@@ -10,7 +10,8 @@ namespace sa {
 // v = acc [+ bias[n]] [* (mask[m, n] > 0)] [relu] [+= C[m, n] (fp32 C only)]
 // -> C[m, n] as fp32 or bf16 (c_bf16).  aug_c0 > 0: also writes C[m, aug_c0
 // .. ldc) = [clip(reward[m], -1, 1), one_hot(action[m]), 0...] (the core-input
-// columns next to the torso FC, experiment.py:191-198).
+// columns next to the torso FC, experiment.py:191-198); an action outside
+// [0, aug_num_actions) gives an all-zero one-hot, as tf.one_hot does.
 struct GemmBf16Epilogue {
   void* C;
   int ldc;
@@ -24,6 +25,7 @@ struct GemmBf16Epilogue {
   const float* aug_reward;
   const int64_t* aug_action;
   int aug_c0;
+  int aug_num_actions;  // one-hot columns that are real; the rest stay 0
 };
 
 int gemm_bf16_splits(int M, int N, int K, int ones_row);

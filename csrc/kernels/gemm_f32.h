@@ -7,7 +7,9 @@ namespace sa {
 
 // v = acc [+ bias[n]] [* (mask[m, n] > 0)] [relu] [+= C[m, n]] -> C[m, n]
 // aug_c0 > 0: also writes C[m, aug_c0 ..ldc) = [clip(reward[m], -1, 1),
-// one_hot(action[m]), 0...] (the core-input columns next to the torso FC).
+// one_hot(action[m]), 0...] (the core-input columns next to the torso FC);
+// an action outside [0, aug_num_actions) gives an all-zero one-hot, as
+// tf.one_hot does.
 struct GemmEpilogue {
   float* C;
   int ldc;
@@ -20,6 +22,7 @@ struct GemmEpilogue {
   const float* aug_reward;
   const int64_t* aug_action;
   int aug_c0;
+  int aug_num_actions;  // one-hot columns that are real; the rest stay 0
 };
 
 // K splits the launch would use (grid.z) and the partial-slab workspace they

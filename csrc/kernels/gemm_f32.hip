@@ -66,8 +66,11 @@ __device__ __forceinline__ void store_aug(const GemmEpilogue& e, int m, int j) {
   float v = 0.f;
   if (j == 0) {
     v = fminf(fmaxf(e.aug_reward[m], -1.f), 1.f);  // core input: always abs_one
-  } else if (j - 1 == static_cast<int>(e.aug_action[m])) {
-    v = 1.f;
+  } else {
+    // an index outside [0, aug_num_actions) gives a zero row (tf.one_hot);
+    // compared in 64 bits: a cast to int could wrap into range
+    const int64_t act = e.aug_action[m];
+    if (act >= 0 && act < e.aug_num_actions && j - 1 == static_cast<int>(act)) v = 1.f;
   }
   e.C[static_cast<int64_t>(m) * e.ldc + e.aug_c0 + j] = v;
 }

@@ -556,11 +556,14 @@ pybind11::dict actor_core_bf16_info(int64_t R, int64_t K, int64_t A) {
 // = stride(0), unit column stride).  op(A) = A^T when ta (A is [K, M]),
 // op(B) = B^T when tb (B is [N, K]).  colsum: ones-row column sums of op(B)
 // accumulated into it; aug_*: the core-input columns [clip(r), one_hot(a),
-// 0...] written at C[:, aug_c0:] (aug_c0 = N).
+// 0...] written at C[:, aug_c0:] (aug_c0 = N); an action outside
+// [0, aug_num_actions) gives a zero one-hot (aug_num_actions < 0, the
+// default: every column after the reward is a one-hot column).
 void gemm_f32(at::Tensor A, at::Tensor B, bool ta, bool tb, at::Tensor C,
               c10::optional<at::Tensor> bias, c10::optional<at::Tensor> mask, bool relu,
               bool accumulate, c10::optional<at::Tensor> colsum,
-              c10::optional<at::Tensor> aug_reward, c10::optional<at::Tensor> aug_action) {
+              c10::optional<at::Tensor> aug_reward, c10::optional<at::Tensor> aug_action,
+              int64_t aug_num_actions) {
   auto rm = [](const at::Tensor& t, const char* n) {
     TORCH_CHECK(t.is_cuda() && t.dim() == 2 && t.stride(1) == 1 && t.scalar_type() == at::kFloat,
                 n, " must be a row-major float32 GPU matrix");
@@ -605,6 +608,11 @@ void gemm_f32(at::Tensor A, at::Tensor B, bool ta, bool tb, at::Tensor C,
     ep.aug_reward = aug_reward->data_ptr<float>();
     ep.aug_action = aug_action->data_ptr<int64_t>();
     ep.aug_c0 = N;
+    // default: every column after the reward is a one-hot column
+    const int64_t cols = C.size(1) - N - 1;
+    TORCH_CHECK(aug_num_actions <= cols, "aug: ", aug_num_actions, " actions in ", cols,
+                " columns");
+    ep.aug_num_actions = aug_num_actions < 0 ? cols : aug_num_actions;
   }
   const c10::DeviceGuard guard(A.device());
   const int splits = sa::gemm_f32_splits(M, N, K, ones);
@@ -625,7 +633,8 @@ void gemm_f32(at::Tensor A, at::Tensor B, bool ta, bool tb, at::Tensor C,
 void gemm_bf16(at::Tensor A, at::Tensor B, bool ta, bool tb, at::Tensor C,
                c10::optional<at::Tensor> bias, c10::optional<at::Tensor> mask, bool relu,
                bool accumulate, c10::optional<at::Tensor> colsum,
-               c10::optional<at::Tensor> aug_reward, c10::optional<at::Tensor> aug_action) {
+               c10::optional<at::Tensor> aug_reward, c10::optional<at::Tensor> aug_action,
+               int64_t aug_num_actions) {
   auto rm = [](const at::Tensor& t, const char* n, bool want_bf16) {
     TORCH_CHECK(t.is_cuda() && t.dim() == 2 && t.stride(1) == 1, n,
                 " must be a row-major GPU matrix");
@@ -676,6 +685,11 @@ void gemm_bf16(at::Tensor A, at::Tensor B, bool ta, bool tb, at::Tensor C,
     ep.aug_reward = aug_reward->data_ptr<float>();
     ep.aug_action = aug_action->data_ptr<int64_t>();
     ep.aug_c0 = N;
+    // default: every column after the reward is a one-hot column
+    const int64_t cols = C.size(1) - N - 1;
+    TORCH_CHECK(aug_num_actions <= cols, "aug: ", aug_num_actions, " actions in ", cols,
+                " columns");
+    ep.aug_num_actions = aug_num_actions < 0 ? cols : aug_num_actions;
   }
   const c10::DeviceGuard guard(A.device());
   const int splits = sa::gemm_bf16_splits(M, N, K, ones);
@@ -804,13 +818,15 @@ void register_learner_ops(pybind11::module& m) {
         pybind11::arg("mask") = pybind11::none(), pybind11::arg("relu") = false,
         pybind11::arg("accumulate") = false, pybind11::arg("colsum") = pybind11::none(),
         pybind11::arg("aug_reward") = pybind11::none(),
-        pybind11::arg("aug_action") = pybind11::none());
+        pybind11::arg("aug_action") = pybind11::none(),
+        pybind11::arg("aug_num_actions") = -1);
   m.def("gemm_bf16", &gemm_bf16, pybind11::arg("A"), pybind11::arg("B"), pybind11::arg("ta"),
         pybind11::arg("tb"), pybind11::arg("C"), pybind11::arg("bias") = pybind11::none(),
         pybind11::arg("mask") = pybind11::none(), pybind11::arg("relu") = false,
         pybind11::arg("accumulate") = false, pybind11::arg("colsum") = pybind11::none(),
         pybind11::arg("aug_reward") = pybind11::none(),
-        pybind11::arg("aug_action") = pybind11::none());
+        pybind11::arg("aug_action") = pybind11::none(),
+        pybind11::arg("aug_num_actions") = -1);
   // read-only: the path gemm_f32 / gemm_bf16 take for a shape (the launchers'
   // own decision functions)
   m.def("gemm_f32_info", [](int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldb, bool ta,

@@ -82,7 +82,8 @@ class _CoreLSTM(torch.autograd.Function):
     # in its epilogue)
     h_aug = torch.empty(N, ld, dtype=bf, device=feats.device)
     C.gemm_bf16(feats, w16_fc, False, False, h_aug, bias=b_fc, relu=True,
-                aug_reward=rewards, aug_action=actions)
+                aug_reward=rewards, aug_action=actions,
+                aug_num_actions=num_actions)
     if instr_enc is not None:
       h_aug[:, c_instr:f_in].copy_(instr_enc)
     wx16 = kernel[:K].to(bf) if w16 is None else w16[1][:K]
@@ -179,7 +180,8 @@ def core_input_f32(feats, w_fc, b_fc, rewards, actions, num_actions,
   h_aug = torch.empty(feats.shape[0], K, dtype=torch.float32,
                       device=feats.device)
   ext().gemm_f32(feats, w_fc, False, False, h_aug, bias=b_fc, relu=True,
-                 aug_reward=rewards, aug_action=actions)
+                 aug_reward=rewards, aug_action=actions,
+                 aug_num_actions=num_actions)
   if instr_enc is not None:
     h_aug[:, f_in - 64:f_in].copy_(instr_enc)
   return h_aug
@@ -198,7 +200,8 @@ def core_input_bf16(feats, w16_fc, b_fc, rewards, actions, num_actions,
   h_aug = torch.empty(feats.shape[0], (K + 15) // 16 * 16,
                       dtype=torch.float32, device=feats.device)
   ext().gemm_bf16(feats, w16_fc, False, False, h_aug, bias=b_fc, relu=True,
-                  aug_reward=rewards, aug_action=actions)
+                  aug_reward=rewards, aug_action=actions,
+                  aug_num_actions=num_actions)
   if instr_enc is not None:
     h_aug[:, f_in - 64:f_in].copy_(instr_enc)
   return h_aug, K
