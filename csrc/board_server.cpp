@@ -9,15 +9,19 @@
 //
 //   futex-wait on the board's sequence word -> collect REQUEST slots (for
 //   up to a short batching window while fewer than min_ready are ready) ->
-//   row mask into pinned memory -> H2D of the whole input region + mask ->
-//   hipGraphLaunch of the captured graph (plain or with-instruction variant,
-//   picked from the instruction lengths) -> D2H of each ready slot's output
-//   block -> wait on this batch's event -> RESPONSE + futex wake per slot.
-// The row mask normally lives in the board's input region (one H2D carries
-// it), and with set_direct_output the graph's epilogue writes the ready rows
-// straight into the registered host board, so a launch is ONE copy and one
-// graph: the per-slot D2H copies cost ~40-150 us each on the queue
-// (profiles/r6_e2e.md).
+//   row mask -> memcpy of the whole input region into its pinned mirror ->
+//   H2D of the mirror + mask -> hipGraphLaunch of the captured graph (plain
+//   or with-instruction variant, picked from the instruction lengths) -> D2H
+//   of each ready slot's output block into the pinned output mirror -> wait
+//   on this batch's event -> memcpy of the slots' valid rows into the board
+//   -> RESPONSE + futex wake per slot.
+// The board itself is pageable shared memory (its workers are forked before
+// the GPU is initialised), so every DMA goes through the pinned mirrors the
+// Python side allocates (set_staging).  The row mask normally lives in the
+// board's input region (one H2D carries it), and with set_direct_output the
+// graph's epilogue writes the ready rows straight into the output mirror, so
+// a launch is ONE copy and one graph: the per-slot D2H copies cost ~40-150 us
+// each on the queue (profiles/r6_e2e.md).
 //
 // Depth 2 (add_buffer, a second set of device buffers and graphs): batch k+1
 // is enqueued before batch k is answered.  Its input H2D runs on a copy
@@ -132,6 +136,32 @@ class NativeBoardServer {
     if (thread_.joinable()) thread_.join();
   }
 
+  // the pinned mirrors every DMA goes through: one input mirror (in_bytes)
+  // per buffer set, one output mirror (num_slots * slot_out_bytes; with
+  // direct output the graphs were captured writing into it), and the layout
+  // of a slot's output block (offset and bytes per row of each field), by
+  // which finish() moves a slot's valid rows into the board; after the last
+  // add_buffer, before start()
+  void set_staging(const std::vector<uintptr_t>& in_pinned, uintptr_t out_pinned,
+                   const std::vector<int64_t>& out_offsets,
+                   const std::vector<int64_t>& out_row_bytes) {
+    TORCH_CHECK(!thread_.joinable(), "set_staging after start");
+    TORCH_CHECK(in_pinned.size() == bufs_.size(), "one input mirror per buffer set");
+    TORCH_CHECK(out_pinned, "null output mirror");
+    TORCH_CHECK(out_offsets.size() == out_row_bytes.size(), "output layout");
+    for (size_t f = 0; f < out_offsets.size(); ++f)
+      TORCH_CHECK(out_offsets[f] >= 0 && out_row_bytes[f] >= 0 &&
+                      out_offsets[f] + M_ * out_row_bytes[f] <= so_,
+                  "output field outside the slot's block");
+    for (size_t k = 0; k < bufs_.size(); ++k) {
+      TORCH_CHECK(in_pinned[k], "null input mirror");
+      bufs_[k].in_pin = reinterpret_cast<uint8_t*>(in_pinned[k]);
+    }
+    out_pin_ = reinterpret_cast<uint8_t*>(out_pinned);
+    out_off_ = out_offsets;
+    out_row_ = out_row_bytes;
+  }
+
   // batching window (see serve): launch once >= min_ready slots are ready
   // or gather_us microseconds after the first one; gather_us 0 = off
   void set_batching(int64_t min_ready, int64_t gather_us) {
@@ -139,7 +169,7 @@ class NativeBoardServer {
     gather_us_ = gather_us < 0 ? 0 : (gather_us > 100000 ? 100000 : gather_us);
   }
   // direct output: the graph's epilogue writes the ready rows into the
-  // host board itself, so no D2H copy per slot (before start)
+  // output mirror itself, so no D2H copy per slot (before start)
   void set_direct_output(bool on) { direct_out_ = on; }
   int64_t gathered() const { return gathered_.load(); }
   int64_t depth() const { return static_cast<int64_t>(bufs_.size()); }
@@ -238,6 +268,7 @@ class NativeBoardServer {
   // enqueue one batch over the ready_ slots into buffer set k; returns rows
   int64_t launch(int k) {
     Buf& b = bufs_[k];
+    if (!b.in_pin || !out_pin_) fail("no pinned staging (set_staging)");
     const int64_t R = S_ * M_;
     std::memset(b.mask_host, 0, sizeof(float) * R);
     int64_t rows = 0;
@@ -257,13 +288,15 @@ class NativeBoardServer {
     hipGraphExec_t g = instr ? b.instr : b.plain;
     if (!g) fail(instr ? "no with-instruction graph captured" : "no plain graph captured");
     if (!b.done_ev) check(hipEventCreateWithFlags(&b.done_ev, hipEventDisableTiming), "hipEventCreate");
+    // set k's previous batch is answered, so no copy still reads its mirror
+    std::memcpy(b.in_pin, base_ + hdr_, in_bytes_);
     if (bufs_.size() > 1) {
       // set k's previous batch is answered (its event waited), so its
-      // input buffers are free: copy on the copy stream, under the graph
+      // device inputs are free: copy on the copy stream, under the graph
       // of the batch in flight
       if (!copy_) check(hipStreamCreateWithFlags(&copy_, hipStreamNonBlocking), "hipStreamCreate");
       if (!b.in_ev) check(hipEventCreateWithFlags(&b.in_ev, hipEventDisableTiming), "hipEventCreate");
-      check(hipMemcpyAsync(b.in_dev, base_ + hdr_, in_bytes_, hipMemcpyHostToDevice, copy_),
+      check(hipMemcpyAsync(b.in_dev, b.in_pin, in_bytes_, hipMemcpyHostToDevice, copy_),
             "board H2D");
       if (!b.mask_in_board)
         check(hipMemcpyAsync(b.mask_dev, b.mask_host, sizeof(float) * R, hipMemcpyHostToDevice,
@@ -272,7 +305,7 @@ class NativeBoardServer {
       check(hipEventRecord(b.in_ev, copy_), "hipEventRecord");
       check(hipStreamWaitEvent(stream_, b.in_ev, 0), "hipStreamWaitEvent");
     } else {
-      check(hipMemcpyAsync(b.in_dev, base_ + hdr_, in_bytes_, hipMemcpyHostToDevice, stream_),
+      check(hipMemcpyAsync(b.in_dev, b.in_pin, in_bytes_, hipMemcpyHostToDevice, stream_),
             "board H2D");
       if (!b.mask_in_board)
         check(hipMemcpyAsync(b.mask_dev, b.mask_host, sizeof(float) * R, hipMemcpyHostToDevice,
@@ -280,10 +313,9 @@ class NativeBoardServer {
               "mask H2D");
     }
     check(hipGraphLaunch(g, stream_), "hipGraphLaunch");
-    uint8_t* host_out = base_ + hdr_ + in_bytes_;
     if (!direct_out_)
       for (int64_t s : ready_)
-        check(hipMemcpyAsync(host_out + s * so_, b.out_dev + s * so_, so_, hipMemcpyDeviceToHost,
+        check(hipMemcpyAsync(out_pin_ + s * so_, b.out_dev + s * so_, so_, hipMemcpyDeviceToHost,
                              stream_),
               "slot D2H");
     // an event of this batch, not a stream synchronise: the learner thread
@@ -297,7 +329,14 @@ class NativeBoardServer {
   // wait for the batch in flight and answer its slots
   void finish() {
     check(hipEventSynchronize(bufs_[pend_buf_].done_ev), "hipEventSynchronize");
+    uint8_t* host_out = base_ + hdr_ + in_bytes_;
     for (int64_t s : pend_slots_) {
+      // the slot's valid rows: output mirror -> board
+      int64_t n = __atomic_load_n(&words_[16 + S_ + s], __ATOMIC_ACQUIRE);
+      n = n < 0 ? 0 : (n > M_ ? M_ : n);
+      for (size_t f = 0; f < out_off_.size(); ++f)
+        std::memcpy(host_out + s * so_ + out_off_[f], out_pin_ + s * so_ + out_off_[f],
+                    n * out_row_[f]);
       inflight_[s] = 0;
       __atomic_store_n(&words_[16 + s], kResponse, __ATOMIC_RELEASE);
       futex(&words_[16 + s], FUTEX_WAKE, INT_MAX, nullptr);
@@ -326,6 +365,7 @@ class NativeBoardServer {
     hipGraphExec_t plain = nullptr, instr = nullptr;
     hipEvent_t done_ev = nullptr, in_ev = nullptr;
     bool mask_in_board = false;
+    uint8_t* in_pin = nullptr;  // pinned mirror of the board's inputs
   };
 
   uint8_t* base_;
@@ -333,6 +373,8 @@ class NativeBoardServer {
   int64_t hdr_, in_bytes_, so_, S_, M_, instr_off_;
   hipStream_t stream_;
   hipStream_t copy_ = nullptr;  // depth 2: the input H2D
+  uint8_t* out_pin_ = nullptr;  // pinned mirror of the board's outputs
+  std::vector<int64_t> out_off_, out_row_;  // a slot's output fields
   int device_;
   std::vector<Buf> bufs_;
   std::vector<int64_t> ready_, pend_slots_;
@@ -369,6 +411,8 @@ void register_board_server(pybind11::module& m) {
            py::arg("mask_dev"), py::arg("mask_host"), py::arg("exec_plain"),
            py::arg("exec_instr"))
       .def("depth", &NativeBoardServer::depth)
+      .def("set_staging", &NativeBoardServer::set_staging, py::arg("in_pinned"),
+           py::arg("out_pinned"), py::arg("out_offsets"), py::arg("out_row_bytes"))
       .def("set_direct_output", &NativeBoardServer::set_direct_output, py::arg("on"))
       .def("set_batching", &NativeBoardServer::set_batching, py::arg("min_ready"),
            py::arg("gather_us"))

@@ -10,9 +10,9 @@
 //     slab currently being filled, writes its unroll straight into
 //     [t, b, ...] step by step, and Commit()s; the B-th commit publishes the
 //     slab (READY, FIFO by fill order);
-//   * the consumer (learner) Acquire()s a READY slab, moves it to HBM with
-//     ONE hipMemcpyAsync (the shm is hipHostRegister'ed, so the copy is a DMA
-//     from the producers' pages), and Release()s it once that copy is done.
+//   * the consumer (learner) Acquire()s a READY slab, memcpys it into a
+//     pinned buffer of its own (the shm is pageable), Release()s it, and
+//     moves the buffer to HBM with ONE hipMemcpyAsync.
 //
 // States: FREE -> FILLING (columns being claimed/written) -> READY (all B
 // committed) -> READING (consumer) -> FREE.  Column hand-out and slab

@@ -74,8 +74,9 @@ __global__ __launch_bounds__(256) void actor_head_sample_kernel(
 //   out[(r / M) * slot_bytes + off[f] + (r % M) * per[f] + b] = src_f[r][b]
 // for every field f < nf (per-row byte counts multiples of 4).
 // masked_only: rows whose mask is 0 are not packed (`out` may then be the
-// device view of the board's registered HOST output region: a slot that did
-// not ask may be being read by its worker right now), and each packing
+// device view of the pinned HOST mirror of the board's output region: the
+// server moves only the asking slots' rows from it into the board, while a
+// second buffer set's graph may be writing other slots' rows), and each packing
 // thread ends with a system-scope fence so the host sees the rows once the
 // launch's completion event fires.  This replaces one D2H copy per ready
 // slot (each ~6 us, but 40-150 us apart on the queue: profiles/r6_e2e.md).

@@ -296,7 +296,7 @@ std::vector<at::Tensor> actor_head_sample(at::Tensor h, at::Tensor wp, at::Tenso
 // dtype, 4-byte multiple per row) packed into `out` (uint8, S slot blocks of
 // slot_bytes) at byte offset offs[f] + (r % M) * row_bytes(f) of slot r / M.
 // out_addr != 0: pack into that device-accessible address instead of `out`
-// (the board's registered host output region, out.numel() bytes long; only
+// (the pinned host mirror of the board's output region, out.numel() bytes long; only
 // the rows whose mask is set are written, then fenced at system scope).
 void board_epilogue(std::vector<at::Tensor> fields, std::vector<int64_t> offs, at::Tensor out,
                     int64_t M, int64_t slot_bytes, at::Tensor mask, at::Tensor c2,

@@ -347,15 +347,15 @@ class _TrajFeeder(object):
   """Learner side of the trajectory queue (runtime/traj_queue.py).
 
   Per step: acquire a full slab (one [T+1, B] batch the actors wrote in
-  place), ONE async H2D copy of it into the idle device slot on a copy
+  place), move it into the idle slot's pinned staging buffer (the slabs are
+  shared pageable memory; the slab is released right after this memcpy),
+  ONE async H2D copy of that buffer into the idle device slot on a copy
   stream, the compute stream waits on that copy's event and replays the
   slot's captured learner graph.  While step k computes on slot k % 2 the
   copy of step k+1 lands in the other slot (StagingArea, experiment.py:
-  587-597).  A slab is released as soon as its copy event has completed
-  (polled: the host never waits on compute)."""
+  587-597)."""
 
   def __init__(self, tq, learner, device, use_graph):
-    import collections
     import torch
     self.torch = torch
     self.tq = tq
@@ -368,11 +368,14 @@ class _TrajFeeder(object):
                   for _ in range(n)]
     self.views = [tq.layout.torch_views(s) for s in self.slots]
     self.graphs = [None] * n
-    self.pending = collections.deque()
     self.k = 0
     self.host_sync = measure_env('SA_H2D_SYNC', 'host') != 'device'
     if self.cuda:
       self.copy_stream = _h2d_stream(device)
+      # pinned host memory the H2D copies read, one buffer per device slot
+      self.stage = [torch.empty(tq.layout.nbytes, dtype=torch.uint8).pin_memory()
+                    for _ in range(n)]
+      self.copied = [None] * n  # the latest H2D copy out of each buffer
       self.free = [torch.cuda.Event() for _ in range(n)]
       for e in self.free:
         e.record()
@@ -392,25 +395,13 @@ class _TrajFeeder(object):
                         learner._static_loss,
                         getattr(learner, '_graph_keep', None))
 
-  def _reap(self, block):
-    while self.pending:
-      slab, ev = self.pending[0]
-      if not ev.query():
-        if not block:
-          return
-        ev.synchronize()
-      self.pending.popleft()
-      self.tq.release(slab)
-      block = False
-
   def step(self, timeout_s, poison=False, check=None):
     """-> (loss, host info dict, seconds waited for a full slab).
-    self.last_host_s: host time of the step's data path (slab hand-off,
-    H2D enqueue, graph launch, slab release) excluding the wait."""
+    self.last_host_s: host time of the step's data path (slab hand-off and
+    staging memcpy, H2D enqueue, graph launch) excluding the wait."""
     torch = self.torch
     t0 = time.time()
     while True:
-      self._reap(block=False)
       slab = self.tq.acquire(timeout_ms=200)
       if slab >= 0:
         break
@@ -439,6 +430,10 @@ class _TrajFeeder(object):
       self.last_host_s = time.time() - t1
       return loss, info, wait
     j = self.k % 2
+    if self.copied[j] is not None:
+      self.copied[j].synchronize()  # the buffer's previous copy has read it
+    self.stage[j].copy_(self.tq.host_tensor(slab))
+    self.tq.release(slab)
     # host-side ordering (as bench.py): device-side waits between the copy
     # and compute streams cost 0.15-0.2 ms per learner step plus outliers;
     # the host instead waits for slot j's last graph before the copy and for
@@ -449,7 +444,7 @@ class _TrajFeeder(object):
         self.free[j].synchronize()
       else:
         self.copy_stream.wait_event(self.free[j])  # slot j's last graph is done
-      self.slots[j].copy_(self.tq.host_tensor(slab), non_blocking=True)
+      self.slots[j].copy_(self.stage[j], non_blocking=True)
       copied = torch.cuda.Event()
       copied.record(self.copy_stream)
     comp = torch.cuda.current_stream(self.device)
@@ -457,7 +452,7 @@ class _TrajFeeder(object):
       copied.synchronize()
     else:
       comp.wait_event(copied)
-    self.pending.append((slab, copied))
+    self.copied[j] = copied
     if self.use_graph:
       if self.graphs[j] is None:
         copied.synchronize()  # capture runs on the data in place
@@ -474,28 +469,8 @@ class _TrajFeeder(object):
       loss = learner.step(self.views[j])
     self.free[j].record(comp)
     self.k += 1
-    self._reap(block=len(self.pending) > 2)
     self.last_host_s = time.time() - t1
     return loss, info, wait
-
-  def close(self):
-    self._reap(block=True)
-
-  def drain(self, timeout_s=10.0):
-    """Waits (bounded, polling) until every H2D copy still reading a host
-    slab has completed -> True; False if one is still in flight at the
-    deadline (e.g. after a GPU fault), when the slabs must stay registered."""
-    if not self.cuda:
-      return True
-    deadline = time.time() + timeout_s
-    while self.pending:
-      if self.pending[0][1].query():
-        self.pending.popleft()  # the queue is closing: no release needed
-        continue
-      if time.time() > deadline:
-        return False
-      time.sleep(0.001)
-    return True
 
 
 # --------------------------------------------------------------- train
@@ -703,7 +678,6 @@ def train(flags):
   elif use_groups:
     use_traj = True
     actor_errors = []
-    tq.pin()
     feeder = _TrajFeeder(tq, learner, device,
                          flags.use_hip_graph and device.type == 'cuda')
     feeder.prepare()
@@ -768,8 +742,7 @@ def train(flags):
       layout = BatchLayout(flags.unroll_length + 1, flags.batch_size,
                            frame_shape, num_actions, use_instruction=use_instr)
       num_slabs = max(3, -(-flags.num_actors // flags.batch_size) + 2)
-      tq = TrajectoryQueue(layout, num_slabs,
-                           pin_device=device if device.type == 'cuda' else None)
+      tq = TrajectoryQueue(layout, num_slabs)
       feeder = _TrajFeeder(tq, learner, device,
                            flags.use_hip_graph and device.type == 'cuda')
       feeder.prepare()
@@ -831,7 +804,6 @@ def train(flags):
   use_graph = flags.use_hip_graph and device.type == 'cuda'
   staging = dev_stage = copied = None
   host_ms, loop_ms = [], []
-  failed = False
   try:
     frames = int(learner.frames.item())
     while frames < flags.total_environment_frames:
@@ -989,17 +961,10 @@ def train(flags):
   except _Terminated:
     log.warning('SIGTERM: stopping and checkpointing at %d frames',
                 int(learner.frames.item()))
-  except BaseException:
-    failed = True
-    raise
   finally:
     stop.set()
     if use_traj:
-      # every in-flight H2D of a host slab must finish before the slabs are
-      # unregistered; after a failure the wait is bounded (a GPU fault may
-      # never complete the copies: then the slabs stay registered)
-      drained = feeder.drain(10.0 if failed else 600.0)
-      tq.close(unregister=drained)
+      tq.close()
     if infer is not None:
       infer.close()
     if groups is not None:

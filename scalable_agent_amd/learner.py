@@ -442,11 +442,12 @@ class Learner:
 def _gather_targets(targets, tasks):
   """All ranks' PopArt targets/tasks (so every replica updates identically)."""
   import torch.distributed as dist
+  from .parallel.dist import all_gather
   world = dist.get_world_size()
   t_all = [torch.empty_like(targets) for _ in range(world)]
   k_all = [torch.empty_like(tasks) for _ in range(world)]
-  dist.all_gather(t_all, targets.contiguous())
-  dist.all_gather(k_all, tasks.contiguous())
+  all_gather(t_all, targets.contiguous())
+  all_gather(k_all, tasks.contiguous())
   return torch.cat(t_all, 1), torch.cat(k_all, 0)
 
 

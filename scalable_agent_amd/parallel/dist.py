@@ -78,9 +78,59 @@ def cleanup():
     dist.destroy_process_group()
 
 
+def host_staged(t, group=None):
+  """True when a collective on `t` must go through host memory: gloo takes
+  CPU tensors only, so the one-card rehearsal of the multi-rank GPU path
+  (SA_DIST_BACKEND=gloo) copies to the host, reduces there and copies back."""
+  return t.is_cuda and dist.get_backend(group) == 'gloo'
+
+
+class _HostStagedWork(object):
+  """An all-reduce of a GPU tensor by gloo, through a host copy.  The copy
+  to the host waits for the current stream's work on `t`; wait() ends the
+  collective and copies the result back on the then-current stream."""
+
+  def __init__(self, t, op, group):
+    self.t = t
+    self.host = t.detach().cpu()
+    self.work = dist.all_reduce(self.host, op=op, group=group, async_op=True)
+
+  def wait(self):
+    self.work.wait()
+    self.t.copy_(self.host)
+
+
+def all_reduce(t, op=None, group=None, async_op=False):
+  """dist.all_reduce (in place) that hands gloo CPU tensors only."""
+  op = dist.ReduceOp.SUM if op is None else op
+  if not host_staged(t, group):
+    return dist.all_reduce(t, op=op, group=group, async_op=async_op)
+  work = _HostStagedWork(t, op, group)
+  if async_op:
+    return work
+  work.wait()
+  return None
+
+
+def all_gather(out, t, group=None):
+  """dist.all_gather that hands gloo CPU tensors only."""
+  if not host_staged(t, group):
+    dist.all_gather(out, t, group=group)
+    return
+  host = [torch.empty_like(o, device='cpu') for o in out]
+  dist.all_gather(host, t.detach().cpu(), group=group)
+  for o, h in zip(out, host):
+    o.copy_(h)
+
+
 def broadcast_params(flat_params, src=0, group=None):
   """Initial weight broadcast so every replica starts identical."""
   if dist.is_initialized() and dist.get_world_size(group) > 1:
+    if host_staged(flat_params, group):
+      host = flat_params.detach().cpu()
+      dist.broadcast(host, src=src, group=group)
+      flat_params.copy_(host)
+      return
     dist.broadcast(flat_params, src=src, group=group)
 
 
@@ -92,8 +142,8 @@ def param_checksum_consistent(flat_params, group=None, rtol=0.0):
                    flat_params.double().abs().sum()])
   mx = s.clone()
   mn = s.clone()
-  dist.all_reduce(mx, op=dist.ReduceOp.MAX, group=group)
-  dist.all_reduce(mn, op=dist.ReduceOp.MIN, group=group)
+  all_reduce(mx, op=dist.ReduceOp.MAX, group=group)
+  all_reduce(mn, op=dist.ReduceOp.MIN, group=group)
   return bool(torch.all((mx - mn).abs() <= rtol * mx.abs()))
 
 
@@ -154,7 +204,8 @@ class GradientSynchronizer:
     (async_op=False): ProcessGroupNCCL runs them on the CURRENT stream, so
     the caller's stream - the stream plan's early stream with its own
     hardware queue, or the compute stream - decides where they run
-    (parallel/streams.py).  gloo keeps async work handles."""
+    (parallel/streams.py).  gloo keeps async work handles (of host copies
+    for GPU tensors: all_reduce above)."""
     g = self.flat.grads
     return g.is_cuda and dist.get_backend(self.group) == 'nccl'
 
@@ -172,8 +223,8 @@ class GradientSynchronizer:
       done.record()
       self._works = [done]
     else:
-      self._works = [dist.all_reduce(g, op=self.op, group=self.group,
-                                     async_op=True)]
+      self._works = [all_reduce(g, op=self.op, group=self.group,
+                                async_op=True)]
 
   def all_reduce(self):
     """Reduces what begin_early did not and leaves the current stream
@@ -194,8 +245,8 @@ class GradientSynchronizer:
       if self._stream_ordered():
         dist.all_reduce(late, op=self.op, group=self.group)
       else:
-        works = works + [dist.all_reduce(late, op=self.op, group=self.group,
-                                         async_op=True)]
+        works = works + [all_reduce(late, op=self.op, group=self.group,
+                                    async_op=True)]
       for w in works:
         if not isinstance(w, torch.cuda.Event):
           w.wait()
@@ -208,10 +259,10 @@ class GradientSynchronizer:
       self._mark_start()
     if len(self.buckets) == 1 or self._stream_ordered():
       for lo, hi in (self.buckets if len(self.buckets) > 1 else [(0, None)]):
-        dist.all_reduce(g[lo:hi], op=self.op, group=self.group)
+        all_reduce(g[lo:hi], op=self.op, group=self.group)
     else:
-      works = [dist.all_reduce(g[lo:hi], op=self.op, group=self.group,
-                               async_op=True)
+      works = [all_reduce(g[lo:hi], op=self.op, group=self.group,
+                          async_op=True)
                for lo, hi in self.buckets]
       for w in works:
         w.wait()

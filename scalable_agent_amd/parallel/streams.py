@@ -114,7 +114,8 @@ def warmup_collective(device, group=None):
   if not dist.is_initialized():
     return
   device = torch.device(device)
-  if device.type != 'cuda':
+  if device.type != 'cuda' or dist.get_backend(group) == 'gloo':
+    # gloo takes CPU tensors only (parallel/dist.py host_staged)
     t = torch.ones(1)
     dist.all_reduce(t, group=group)
     return

@@ -44,14 +44,15 @@ class SharedWeights(object):
   `version` (number of completed publishes; 0 = none yet).
 
   Learner: `publish(flat_params)` enqueues ONE async D2H copy, ordered after
-  the learner's stream, into the buffer that is NOT `latest`, straight from
-  the device into the (hipHostRegister-ed) mapping; the next publish (or
-  `flush()`) that finds the copy landed flips `latest` to it.  A publish
-  while the previous copy is still in flight is skipped (the groups take the
-  next one), so `latest` always names a complete snapshot and readers never
-  wait on the learner's GPU work.
-  Group: ActorGroupWorker._sync_weights (copy `latest`, then re-check its
-  seqlock count: a torn copy is discarded)."""
+  the learner's stream, into a pinned buffer of this process (the shared
+  mapping is pageable memory); the next publish (or `flush()`) that finds
+  the copy landed moves it into the buffer that is NOT `latest` and flips
+  `latest` to it.  A publish while the previous copy is still in flight is
+  skipped (the groups take the next one), so `latest` always names a
+  complete snapshot and readers never wait on the learner's GPU work.
+  Group: ActorGroupWorker._sync_weights (`read_into` a pinned buffer of its
+  own: copy `latest`, then re-check its seqlock count, a torn copy is
+  retried)."""
 
   HDR = 4096
   MAGIC = 0x5341574549474854
@@ -80,11 +81,10 @@ class SharedWeights(object):
     self._all = np.frombuffer(self._mm, dtype=np.float32,
                               count=2 * self.numel, offset=self.HDR)
     self.data = [self._all[:self.numel], self._all[self.numel:]]
-    self._pinned = False
-    self._tensors = None
     self._pending = None
     self._stream = None
     self._snap = None
+    self._host = None  # pinned target of the D2H copy
     self.skipped = 0
 
   # --------------------------------------------------------------- both
@@ -97,26 +97,17 @@ class SharedWeights(object):
   def seq(self, b):
     return int(self._hdr[2 + b])
 
-  def tensors(self, device):
-    """Torch views of the two buffers (host-registered on a GPU device)."""
-    import torch
-    from .traj_queue import _hip_host_register
-    if self._tensors is None:
-      if device.type == 'cuda':
-        self._pinned = _hip_host_register(self._all.ctypes.data,
-                                          8 * self.numel)
-      self._tensors = [torch.from_numpy(d) for d in self.data]
-    return self._tensors
-
   # --------------------------------------------------------------- learner
   def _finish(self, block):
     if self._pending is None:
       return True
-    b, ev = self._pending
+    src, ev = self._pending
     if not block and not ev.query():
       return False
     ev.synchronize()
     self._pending = None
+    b = self._target()
+    self.data[b][...] = src
     self._hdr[2 + b] += 1  # even: complete
     self._hdr[0] = b
     self._hdr[1] += 1
@@ -130,15 +121,12 @@ class SharedWeights(object):
   def publish(self, flat_params):
     import torch
     if not flat_params.is_cuda:
-      b = self._target()
-      self.data[b][...] = flat_params.detach().numpy()
-      self._pending = (b, _Done())
+      self._pending = (flat_params.detach().numpy(), _Done())
       self._finish(block=True)
       return True
     if not self._finish(block=False):
       self.skipped += 1
       return False
-    host = self.tensors(flat_params.device)
     if self._stream is None:
       self._stream = torch.cuda.Stream(flat_params.device)
     # the D2H reads a device-side snapshot taken on the learner's stream (a
@@ -149,14 +137,15 @@ class SharedWeights(object):
     cur = torch.cuda.current_stream(flat_params.device)
     if self._snap is None or self._snap.shape != flat_params.shape:
       self._snap = torch.empty_like(flat_params.detach())
+      self._host = torch.empty(self._snap.shape, dtype=self._snap.dtype,
+                               pin_memory=True)
     self._snap.copy_(flat_params.detach())
     self._stream.wait_stream(cur)
-    b = self._target()
     with torch.cuda.stream(self._stream):
-      host[b].copy_(self._snap, non_blocking=self._pinned)
+      self._host.copy_(self._snap, non_blocking=True)
       ev = torch.cuda.Event()
       ev.record(self._stream)
-    self._pending = (b, ev)
+    self._pending = (self._host.numpy(), ev)
     return True
 
   def flush(self):
@@ -180,7 +169,6 @@ class SharedWeights(object):
 
   def close(self):
     self.flush() if self._owner else None
-    self._tensors = None
     self.data = self._all = self._hdr = None
     try:
       self._mm.close()
@@ -304,10 +292,10 @@ class ActorGroupWorker(object):
 
   # ------------------------------------------------------------ weights
   def _sync_weights(self, model, state):
-    """Non-blocking fetch of a newer snapshot: an async H2D of the `latest`
-    buffer into a staging buffer; once it has landed and that buffer's
-    seqlock count is unchanged, a D2D copy (ordered before the next
-    inference) makes it the inference snapshot."""
+    """Fetch of a newer snapshot: a seqlock-checked copy of the `latest`
+    buffer into pinned memory, an async H2D of that into a staging buffer;
+    once it has landed, a D2D copy (ordered before the next inference) makes
+    it the inference snapshot."""
     if self.board_mode:
       state['version'] = max(1, state['version'])  # weights live in the server
       return
@@ -322,35 +310,33 @@ class ActorGroupWorker(object):
         model._refresh_cache()
       return
     if state.get('inflight') is not None:
-      v, b, s, ev = state['inflight']
+      v, ev = state['inflight']
       if not ev.query():
         return
       state['inflight'] = None
-      if w.seq(b) == s:  # not overwritten while the copy ran
-        with torch.cuda.stream(model.stream):
-          model.flat.params.copy_(state['staging'], non_blocking=True)
-          model._refresh_cache()
-        state['version'] = v
+      with torch.cuda.stream(model.stream):
+        model.flat.params.copy_(state['staging'], non_blocking=True)
+        model._refresh_cache()
+      state['version'] = v
       return
     if v == 0 or v == state['version']:
-      return
-    b = w.latest()
-    s = w.seq(b)
-    if s & 1:
       return
     if state.get('staging') is None:
       state['staging'] = torch.empty(w.numel, dtype=torch.float32,
                                      device=model.device)
+      state['host'] = torch.empty(w.numel, dtype=torch.float32,
+                                  pin_memory=True)
       state['copy_stream'] = torch.cuda.Stream(model.device)
-    host = w.tensors(model.device)
+    # no H2D copy is in flight here, so the pinned buffer is free
+    v = w.read_into(state['host'].numpy())
     cs = state['copy_stream']
     # the previous D2D out of the staging buffer must be done first
     cs.wait_stream(model.stream)
     with torch.cuda.stream(cs):
-      state['staging'].copy_(host[b], non_blocking=w._pinned)
+      state['staging'].copy_(state['host'], non_blocking=True)
       ev = torch.cuda.Event()
       ev.record(cs)
-    state['inflight'] = (v, b, s, ev)
+    state['inflight'] = (v, ev)
 
   # ------------------------------------------------------------ loop
   def _loop(self, envs, model, vis, encode_instruction, py_process):

@@ -19,9 +19,14 @@ inference on the GPU (a second GPU context per group) or, with
     wait for request slots -> mask of their rows -> H2D inputs + mask ->
     ONE captured graph over all rows (torso, core, heads + Gumbel sampler; the
     LSTM state of every row resident on the device, updated only where the
-    mask is set) -> the masked rows' outputs -> state 2 + futex wake.  On a
-    GPU the graph's epilogue writes those rows straight into the registered
-    host board (no D2H copy per slot); elsewhere they are copied back.
+    mask is set) -> the masked rows' outputs -> state 2 + futex wake.  The
+    board is pageable shared memory (the workers are forked before the GPU
+    is initialised), so on a GPU the server keeps pinned mirrors of its
+    input and output regions (hipHostMalloc, through torch's pin_memory):
+    inputs go board -> mirror -> device, and the graph's epilogue writes the
+    masked rows straight into the output mirror (no D2H copy per slot), from
+    where the server moves them into the board; elsewhere they are copied
+    back.
     On a GPU with the HIP backend the loop is a C++ thread
     (csrc/board_server.cpp, no Python and no GIL per batch); the graphs are
     captured here first.  SA_BOARD_NATIVE=0 keeps the Python thread.  With
@@ -185,23 +190,24 @@ class BoardServer(object):
       # torch.Generator (inference.py): eager steps, the Python serve loop
       self.use_graph = False
     b = board
-    # the board's input + output regions as host tensors (pinned on a GPU)
+    # the board's input + output regions as host tensors
     self._host_in = torch.from_numpy(b.buf[b.HDR:b.HDR + b.in_bytes])
     self._host_out = torch.from_numpy(b.buf[b.HDR + b.in_bytes:])
-    self.pinned = False
+    # on a GPU: pinned mirrors of the two regions (one input mirror per
+    # buffer set, _buffers; one output mirror: a slot is in one batch at a
+    # time, so the sets' graphs never write the same rows)
+    self.pinned = self.cuda
+    self._pin_in = {}
+    self._pin_out = None
     if self.cuda:
-      from .traj_queue import _hip_host_register
-      torch.cuda.init()
-      self.pinned = _hip_host_register(b.base + b.HDR, b.in_bytes + b.out_bytes)
+      self._pin_out = torch.zeros(b.out_bytes, dtype=torch.uint8).pin_memory()
     self.c = torch.zeros(b.R, b.core, device=dev)
     self.h = torch.zeros(b.R, b.core, device=dev)
     # direct output: the graph's epilogue packs the ready rows into the
-    # registered host board itself (HIP backend on a GPU)
+    # pinned output mirror itself (HIP backend on a GPU)
     self._out_addr = 0
     if self.pinned and getattr(model.agent, 'backend', '') == 'hip':
-      from .traj_queue import _hip_host_device_ptr
-      d = _hip_host_device_ptr(b.base + b.HDR)  # the registration's start
-      self._out_addr = d + b.in_bytes if d else 0
+      self._out_addr = self._pin_out.data_ptr()
     # buffer set 0 (set 1 is allocated by the depth-2 native loop)
     self._sets = [self._buffers(0)]
     (self.in_dev, self.out_dev, self.mask_dev, self.mask_host,
@@ -217,15 +223,19 @@ class BoardServer(object):
 
   @property
   def direct_out(self):
-    """True when the graph writes the responses into the host board."""
+    """True when the graph writes the responses into host memory (the
+    pinned output mirror)."""
     return self._out_addr != 0
 
   def _buffers(self, k):
     """Buffer set k: device inputs, outputs, row mask (device view inside
     the inputs + host) and the typed views of the inputs.  Set 0's host mask
     is the board's own row_mask field, so the input H2D carries it; set 1
-    (depth 2) has a pinned mask of its own, copied after its inputs."""
+    (depth 2) has a pinned mask of its own, copied after its inputs.  On a
+    GPU the set also gets its pinned input mirror (self._pin_in[k])."""
     torch, b, dev = self.torch, self.board, self.model.device
+    if self.cuda:
+      self._pin_in[k] = torch.zeros(b.in_bytes, dtype=torch.uint8).pin_memory()
     # zero-filled: the capture's warm-up steps read the board before any
     # worker wrote it (and a zero mask packs no rows)
     in_dev = torch.zeros(b.in_bytes, dtype=torch.uint8, device=dev)
@@ -254,6 +264,18 @@ class BoardServer(object):
   def native(self):
     """True when the serving loop is the C++ thread."""
     return self._native is not None
+
+  def _out_layout(self):
+    """(offset of each output field in a slot's block, its bytes per row)."""
+    b = self.board
+    return ([o for _, _, _, o, _ in b.out_fields],
+            [nb // b.M for _, _, _, _, nb in b.out_fields])
+
+  def native_staging(self):
+    """NativeBoardServer.set_staging's arguments: the input mirror of every
+    buffer set, the output mirror and the output layout."""
+    return ([self._pin_in[k].data_ptr() for k in range(len(self._sets))],
+            self._pin_out.data_ptr()) + self._out_layout()
 
   def _epilogue_ext(self):
     """The HIP extension when the fused board epilogue applies (HIP
@@ -348,7 +370,8 @@ class BoardServer(object):
         self._host_out.copy_(self.out_dev)
       else:
         with torch.cuda.stream(m.stream):
-          self.in_dev.copy_(self._host_in, non_blocking=self.pinned)
+          self._pin_in[0].copy_(self._host_in)
+          self.in_dev.copy_(self._pin_in[0], non_blocking=True)
           if self.use_graph:
             g = self._graphs.get(has_instr)
             if g is None:
@@ -358,9 +381,15 @@ class BoardServer(object):
             self._body(has_instr)
           so = b.slot_out_bytes
           for s in ready if not self.direct_out else ():
-            self._host_out[s * so:(s + 1) * so].copy_(
-                self.out_dev[s * so:(s + 1) * so], non_blocking=self.pinned)
+            self._pin_out[s * so:(s + 1) * so].copy_(
+                self.out_dev[s * so:(s + 1) * so], non_blocking=True)
           m.stream.synchronize()
+        # the ready slots' valid rows: output mirror -> board
+        for s in ready:
+          n = b.rows_of(s)
+          for o, per in zip(*self._out_layout()):
+            lo = s * so + o
+            self._host_out[lo:lo + n * per].copy_(self._pin_out[lo:lo + n * per])
     for s in ready:
       native.atomic_store_u32(b.state_addr(s), RESPONSE)
       native.futex_wake(b.state_addr(s))
@@ -419,6 +448,7 @@ class BoardServer(object):
           self._graphs[(1, False)].raw_cuda_graph_exec(),
           self._graphs[(1, True)].raw_cuda_graph_exec()
           if m.use_instruction else 0)
+    self._native.set_staging(*self.native_staging())
     self._native.set_direct_output(self.direct_out)
     self._native.set_batching(self.min_ready, self.gather_us)
     self._native.start()

@@ -4,31 +4,30 @@ Replaces the reference's actor -> learner path (experiment.py:530-531
 FIFOQueue(1) + enqueue, :576 dequeue_many, :579-585 time-major transposes,
 :587-597 StagingArea put/get) with:
 
-  actors ──(write [t, b] in place)──> pinned shm slab = ONE learner batch
-  learner ──(ONE hipMemcpyAsync per step, copy stream)──> device slot
+  actors ──(write [t, b] in place)──> shm slab = ONE learner batch
+  learner ──(one memcpy)──> pinned staging buffer
+          ──(ONE hipMemcpyAsync per step, copy stream)──> device slot
                  ──(event)──> captured learner graph
 
 No unroll is ever stacked, transposed or memcpy'd on the host: each actor
 claims a column b of the slab being filled and writes every step's fields
 straight into their time-major position; the B-th commit publishes the slab.
-The slab memory is registered with HIP (hipHostRegister) so the learner's
-copy is a DMA from the actors' pages, overlapped with the previous step's
-compute.
+The slabs are shared (pageable) memory that actor processes forked before
+the GPU was initialised write to, so they cannot be allocated pinned; the
+learner moves a full slab into a pinned buffer of its own (hipHostMalloc,
+through torch's pin_memory) and releases the slab at once, and the DMA from
+that buffer overlaps the previous step's compute.
 
 `BatchLayout` is the flat byte layout of one batch (256-B aligned segments,
 fields in ActorOutput order); the learner's device slots use the same layout,
 so host slab -> device slot is one contiguous copy.
 """
 
-import ctypes
-import logging
 
 import numpy as np
 import torch
 
 from ..structs import ActorOutput, AgentOutput, StepOutput, StepOutputInfo
-
-log = logging.getLogger('scalable_agent_amd')
 
 ALIGN = 256
 
@@ -89,42 +88,6 @@ class BatchLayout(object):
                                   v['baseline']))
 
 
-def _hip_host_register(address, nbytes):
-  """Pins an existing host mapping for async DMA; False if unavailable."""
-  try:
-    lib = ctypes.CDLL('libamdhip64.so')
-  except OSError:
-    return False
-  fn = lib.hipHostRegister
-  fn.restype = ctypes.c_int
-  fn.argtypes = [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint]
-  return fn(ctypes.c_void_p(address), ctypes.c_size_t(nbytes), 0) == 0
-
-
-def _hip_host_device_ptr(address):
-  """Device-side address of registered host memory (None if unavailable)."""
-  try:
-    lib = ctypes.CDLL('libamdhip64.so')
-  except OSError:
-    return None
-  fn = lib.hipHostGetDevicePointer
-  fn.restype = ctypes.c_int
-  fn.argtypes = [ctypes.POINTER(ctypes.c_void_p), ctypes.c_void_p, ctypes.c_uint]
-  out = ctypes.c_void_p()
-  if fn(ctypes.byref(out), ctypes.c_void_p(address), 0) != 0 or not out.value:
-    return None
-  return int(out.value)
-
-
-def _hip_host_unregister(address):
-  try:
-    lib = ctypes.CDLL('libamdhip64.so')
-    lib.hipHostUnregister.argtypes = [ctypes.c_void_p]
-    lib.hipHostUnregister(ctypes.c_void_p(address))
-  except OSError:
-    pass
-
-
 class TrajectoryQueue(object):
   """K slabs of one learner batch each; see the module docstring.
 
@@ -132,7 +95,7 @@ class TrajectoryQueue(object):
   '/name': a named POSIX shm object other processes can attach to.
   """
 
-  def __init__(self, layout, num_slabs, name='', pin_device=None):
+  def __init__(self, layout, num_slabs, name=''):
     from . import native
     self.layout = layout
     self.q = native.TrajQueue(name, int(num_slabs), layout.nbytes, layout.B,
@@ -140,29 +103,9 @@ class TrajectoryQueue(object):
     self.slab_bytes = self.q.slab_bytes
     self._views = [layout.numpy_views(self.q.slab_view(s))
                    for s in range(self.q.num_slabs)]
-    self.pinned = False
-    self._pin_addr = None
-    if pin_device is not None:
-      self.pin()
     self._tensors = [torch.frombuffer(self.q.slab_view(s),
                                       dtype=torch.uint8)[:layout.nbytes]
                      for s in range(self.q.num_slabs)]
-
-  def pin(self):
-    """hipHostRegister the whole payload once: each slab is then a valid
-    async-DMA source (torch sees a pinned pointer).  Call after any fork of
-    producer processes (the registration is per process)."""
-    if self.pinned or not torch.cuda.is_available():
-      return self.pinned
-    torch.cuda.init()
-    self.pinned = _hip_host_register(self.q.payload_address,
-                                     self.q.payload_bytes)
-    if self.pinned:
-      self._pin_addr = self.q.payload_address
-    else:
-      log.warning('hipHostRegister of the trajectory queue failed; the '
-                  'H2D copy will be a staged (pageable) copy')
-    return self.pinned
 
   # ---------------------------------------------------------- producers
   def claim(self, timeout_ms=-1):
@@ -189,7 +132,7 @@ class TrajectoryQueue(object):
     self.q.release(int(slab))
 
   def host_tensor(self, slab):
-    """uint8 tensor over the slab's bytes (pinned when registered)."""
+    """uint8 tensor over the slab's bytes (pageable shared memory)."""
     return self._tensors[slab]
 
   def host_views(self, slab):
@@ -203,11 +146,6 @@ class TrajectoryQueue(object):
   def num_ready(self):
     return self.q.num_ready
 
-  def close(self, unregister=True):
-    """Closes the native queue (wakes every waiter).  unregister=False
-    leaves the payload host-registered: the caller could not prove that no
-    DMA still reads it (unregistering under a live copy can fault the GPU)."""
+  def close(self):
+    """Closes the native queue (wakes every waiter)."""
     self.q.close()
-    if self._pin_addr is not None and unregister:
-      _hip_host_unregister(self._pin_addr)
-      self._pin_addr = None

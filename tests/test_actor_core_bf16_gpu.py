@@ -500,6 +500,7 @@ def test_board_server_native_matches_python_loop(cuda):
           server.mask_dev.data_ptr(), server.mask_host.data_ptr(),
           m.stream.cuda_stream, server._graphs[False].raw_cuda_graph_exec(),
           0, cuda.index or 0)
+      ns.set_staging(*server.native_staging())
       ns.set_direct_output(server.direct_out)
       assert ns.serve_once(10) and ns.rows_served() == 3
     assert board.state(1) == RESPONSE

@@ -70,6 +70,7 @@ def test_native_loop_matches_python_loop(cuda):
           server.mask_dev.data_ptr(), server.mask_host.data_ptr(),
           m.stream.cuda_stream, server._graphs[False].raw_cuda_graph_exec(),
           0, cuda.index or 0)
+      ns.set_staging(*server.native_staging())
       ns.set_direct_output(server.direct_out)
       assert ns.serve_once(10) and ns.rows_served() == 3
     assert board.state(1) == RESPONSE
@@ -138,6 +139,7 @@ def test_depth2_native_loop_matches_python_loop(cuda):
       in1, out1, mask1, mhost1, _ = server._sets[1]
       ns.add_buffer(in1.data_ptr(), out1.data_ptr(), mask1.data_ptr(),
                     mhost1.data_ptr(), g1.raw_cuda_graph_exec(), 0)
+      ns.set_staging(*server.native_staging())
       assert ns.depth() == 2
       native.atomic_store_u32(board.state_addr(0), REQUEST)
       assert ns.serve_once(10, drain=False)
