@@ -570,10 +570,12 @@ at::Tensor maxpool_bwd(at::Tensor dy, at::Tensor arg, int64_t H, int64_t W, int6
 
 at::Tensor frames_f32(at::Tensor x) {
   check_nhwc(x, "frames");
-  TORCH_CHECK(x.scalar_type() == at::kByte && x.size(3) >= 1 && x.size(3) <= 4,
-              "frames must be uint8 NHWC with 1..4 channels");
+  TORCH_CHECK(x.scalar_type() == at::kByte && x.size(3) >= 1 && x.size(3) <= 16,
+              "frames must be uint8 NHWC with 1..16 channels");
   const c10::DeviceGuard g(x.device());
-  auto y = at::empty({x.size(0), x.size(1), x.size(2), 4}, x.options().dtype(at::kFloat));
+  // channels padded to a multiple of 4: 4 for C <= 4, else 8 / 12 / 16
+  auto y = at::empty({x.size(0), x.size(1), x.size(2), (x.size(3) + 3) / 4 * 4},
+                     x.options().dtype(at::kFloat));
   check_size(y, "y");
   sa::cf32::frames_f32_launch(x.data_ptr<uint8_t>(), y.data_ptr<float>(),
                               x.size(0) * x.size(1) * x.size(2), x.size(3), stream());

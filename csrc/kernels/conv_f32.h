@@ -120,7 +120,8 @@ int conv_cu_reserve(int r);
 // CUs the persistent grids are sized for now: 256 - 8 * conv_cu_reserve(-1).
 int conv_cus();
 // Test hook: caps the x dimension of the persistent grids of the direct
-// kernels (conv_fwd, conv_pool_fwd, conv_wgrad, pool_wgrad) at n workgroups,
+// kernels (conv_fwd, conv_pool_fwd, conv_wgrad, pool_wgrad, and the wide-frame
+// frames_wide, wide_conv_pool, wide_pool_wgrad) at n workgroups,
 // so a handful of images gives every workgroup several tiles; for the two
 // weight-gradient kernels the capped grid is also the slot count of the
 // reduction.  0 = no cap (the default: every launch is what it is without
@@ -129,7 +130,8 @@ int conv_cus();
 int conv_grid_cap(int n);
 // Test hook: the last launch of a direct kernel on this host thread.
 // family: conv_fwd, conv_pool_fwd, conv_wgrad, pool_wgrad, maxpool_bwd_blk,
-// maxpool_bwd, frames_tile, frames, shallow_whole (ntiles = images, rows 0),
+// maxpool_bwd, frames_tile, frames, frames_wide, wide_conv_pool,
+// wide_pool_wgrad, shallow_whole (ntiles = images, rows 0),
 // or none (nothing since the last reset:
 // the Winograd launchers took the calls).  rows = R (output / pooled rows per
 // tile); ntiles, rows and tiles_per_img are 0 for the non-persistent kernels.
@@ -269,7 +271,11 @@ bool wgrad_launch(const WgradArgs& a, int K, int S, int src_kind, float* ws,
                   hipStream_t s);
 
 // Fused conv3x3/1 (SAME) + bias + 3x3/2 SAME max-pool: y [N, Hp, Wp, Cout]
-// and argmax codes; the pre-pool conv output only ever lives in LDS.
+// and argmax codes; the pre-pool conv output only ever lives in LDS.  An fp32
+// source of 8, 12 or 16 channels with Cout 16 is the wide-frame stage 0
+// (wide_conv_pool_kernel, family wide_conv_pool; its scatter-form weight
+// gradient, reached through wgrad_launch with pool.arg set, reports
+// wide_pool_wgrad).
 bool conv_pool_fwd_launch(const ConvArgs& a, int src_kind, int pbh, int pbw,
                           float* pooled, uint8_t* arg, hipStream_t s);
 
@@ -300,7 +306,27 @@ bool shallow_fwd_launch(const uint8_t* frames, const float* w1, const float* b1,
 // and 72x128 frames, C 1..4, 1 <= N <= kResBlockMaxFrames, and the LDS plan
 // fits), else 0.  Host arithmetic only.
 int shallow_form(int N, int H, int W, int C);
-// uint8 frames [P pixels][Cs <= 4] -> fp32 [P][4] (x / 255, zero-padded)
+// Wide-frame stage 0 (conv_wide.hip), reached through frames_f32_launch,
+// conv_pool_fwd_launch and wgrad_launch: false where the shape is not covered
+// (nothing launched).  The scatter gradient writes <= kWidePoolWgradSlots
+// slots of ((9 Cp + 16) / 16 * 16) x 16 floats into `ws`.
+constexpr int kWidePoolWgradSlots = 512;
+// Tile height (pooled rows) and LDS row pitch (pixels: >= W + 2 and 5 mod 16)
+// shared by pool_wgrad_kernel and wide_pool_wgrad_kernel
+constexpr int kPwRows = 2;
+__host__ __device__ constexpr int pw_pitch(int W) { return W + 2 + ((5 - (W + 2)) % 16 + 16) % 16; }
+bool wide_conv_pool_launch(const ConvArgs& a, int pbh, int pbw, float* pooled, uint8_t* arg,
+                           hipStream_t s);
+bool wide_pool_wgrad_launch(const WgradArgs& a, float* ws, hipStream_t s);
+void frames_f32_wide_launch(const uint8_t* x, float* y, int64_t P, int Cs, hipStream_t s);
+// conv_f32.hip's grid cap, launch note and slot reduction, for conv_wide.hip
+int wide_grid(int G);
+void wide_note_launch(const char* family, int gx, int ntiles, int rows, int tpi);
+void wide_wgrad_reduce(const float* part, int G, int MT16, int CP, int Cin, float* dw, float* db,
+                       hipStream_t s);
+// uint8 frames [P pixels][Cs <= 4] -> fp32 [P][4] (x / 255, zero-padded);
+// wide frames, 5 <= Cs <= 16: -> fp32 [P][Cs rounded up to a multiple of 4]
+// (frames_f32_wide_kernel, any source alignment; family frames_wide)
 void frames_f32_launch(const uint8_t* x, float* y, int64_t P, int Cs, hipStream_t s);
 // dy *= (ref > 0), fp32, n % 4 == 0
 void relu_mask_launch(float* dy, const float* ref, int64_t n, hipStream_t s);

@@ -118,6 +118,8 @@ __device__ __forceinline__ void lds_get(const float* p, float (&v)[VPL]) {
   } else if constexpr (VPL == 2) {
     const f2 t = *reinterpret_cast<const f2*>(p);
     v[0] = t[0]; v[1] = t[1];
+  } else if constexpr (VPL == 3) {
+    v[0] = p[0]; v[1] = p[1]; v[2] = p[2];
   } else {
     v[0] = *p;
   }
@@ -189,8 +191,11 @@ constexpr int kMaxC = 8;   // staged 16-B chunks per thread per tile
 // and 32-channel layers 9: the 18x24 res32 convs then take 8-row tiles (12
 // MFMA groups = 3 per wave, balanced) instead of 7-row tiles (11 groups:
 // 3,3,3,2 per wave, the short wave idling at the tile barrier)
-__host__ __device__ constexpr int fwd_maxc(int cinp) {
-  return cinp >= 64 ? 16 : (cinp == 32 ? 9 : kMaxC);
+// and the 8x8/4 layer on wide frames (12 / 16 channel image) 13 / 17: its
+// smallest tile, one output row, is 8 image rows of (W - 1) / 4 * 4 + 8 pixels
+__host__ __device__ constexpr int fwd_maxc(int cinp, int K = 3) {
+  return K == 8 && cinp == 12 ? 13 : K == 8 && cinp == 16 ? 17
+         : (cinp >= 64 ? 16 : (cinp == 32 ? 9 : kMaxC));
 }
 
 // Pre-pool gradient at (n, y, x), channels 4ch..4ch+3, gathered from the
@@ -353,7 +358,7 @@ __global__ __launch_bounds__(kThreads, 2) void conv_fwd_kernel(ConvArgs a, int R
   constexpr int VPL = CINP >= 16 ? 4 : CINP / 4;
   constexpr int NB = CINP >= 16 ? CINP / 16 : 1;
   constexpr int KK = K * K;
-  static_assert(CINP == 4 || CINP == 8 || CINP % 16 == 0, "CINP");
+  static_assert(CINP == 4 || CINP == 8 || CINP == 12 || CINP % 16 == 0, "CINP");
   const int Wl = (a.Wo - 1) * S + K;
   const int rows = (R - 1) * S + K;
   const int total = rows * Wl * (CINP / 4);
@@ -399,7 +404,7 @@ __global__ __launch_bounds__(kThreads, 2) void conv_fwd_kernel(ConvArgs a, int R
 
   int tile = blockIdx.x;
   if (tile >= ntiles) return;
-  Stager<CINP, SRC, fwd_maxc(CINP)> st;
+  Stager<CINP, SRC, fwd_maxc(CINP, K)> st;
   auto prefetch = [&](int t) {
     const int n = t / tiles_per_img;
     const int oy0 = (t - n * tiles_per_img) * R;
@@ -948,7 +953,7 @@ __global__ __launch_bounds__(kThreads) void conv_wgrad_kernel(WgradArgs a, int R
 
   // persistent walk with the next tile's x / dY chunks prefetched into
   // registers while the current one computes
-  Stager<CINP, SRC> sx;
+  Stager<CINP, SRC, K == 8 ? fwd_maxc(CINP, K) : kMaxC> sx;
   DyStager<CG, kMaxD, GATHER> sd;
   const int xtotal = rows * Wl * (CINP / 4);
   auto prefetch = [&](int t) {
@@ -1204,14 +1209,12 @@ __global__ __launch_bounds__(256) void wgrad_reduce_kernel(
 // accumulators.  Per-workgroup partials in the wgrad slot layout
 // ([48 rows = tap*4 + ci, row 36 = bias][16 co]), summed by
 // wgrad_reduce_kernel in slot order: bitwise reproducible.
-constexpr int kPwRows = 2;  // pooled rows per tile
 // LDS row pitch (16-B pixels) of the input tile: >= W + 2 and 5 mod 16.  A
 // ds_read_b128 quarter-wave (16 lanes: two adjacent pooled pixels x 8 co)
 // reads inside a 3-row x 5-column window; with the row pitch 5 mod 16 its 15
 // positions fall in 15 distinct 16-B bank slots, so lanes either share an
 // address (broadcast) or a slot never (the W + 2 pitch, 2 mod 16, measured
 // 4.6 bank conflicts per LDS instruction in rocprof).
-__host__ __device__ constexpr int pw_pitch(int W) { return W + 2 + ((5 - (W + 2)) % 16 + 16) % 16; }
 static_assert(pw_pitch(96) == 101 && pw_pitch(84) == 101 && pw_pitch(3) == 5, "pw pitch");
 // x: the fp32 4-channel image, or (u8_cs > 0) the uint8 frames themselves
 // with u8_cs <= 4 channels, scaled by 1/255 on the way into LDS (the same
@@ -1721,7 +1724,7 @@ bool run_conv(const ConvArgs& a, hipStream_t s) {
   double best_cost = 1e30;
   for (int R = 1; R <= a.Ho; ++R) {
     const int rows = (R - 1) * S + K;
-    if (bytes(R) > budget || rows * Wl * (CINP / 4) > fwd_maxc(CINP) * kThreads ||
+    if (bytes(R) > budget || rows * Wl * (CINP / 4) > fwd_maxc(CINP, K) * kThreads ||
         (R * a.Wo + 15) / 16 > 4 * kGmax)
       break;
     const int nt = (a.Ho + R - 1) / R;
@@ -1812,7 +1815,8 @@ bool run_wgrad(const WgradArgs& a, float* ws, hipStream_t s) {
   // tallest tile that fits LDS and the per-thread prefetch registers
   int Rmax = 0;
   for (int R = 1; R <= a.Ho; ++R) {
-    if (bytes(R) > budget || ((R - 1) * S + K) * Wl * (CINP / 4) > kMaxC * kThreads ||
+    if (bytes(R) > budget ||
+        ((R - 1) * S + K) * Wl * (CINP / 4) > (K == 8 ? fwd_maxc(CINP, K) : kMaxC) * kThreads ||
         R * a.Wo * (CG / 4) > kMaxD * kThreads)
       break;
     Rmax = R;
@@ -1834,6 +1838,16 @@ bool run_wgrad(const WgradArgs& a, float* ws, hipStream_t s) {
 }
 
 }  // namespace
+
+// the direct launchers' test hooks and slot reduction, for conv_wide.hip
+int wide_grid(int G) { return capped(G); }
+void wide_note_launch(const char* family, int gx, int ntiles, int rows, int tpi) {
+  note_launch(family, gx, 1, ntiles, rows, tpi);
+}
+void wide_wgrad_reduce(const float* part, int G, int MT16, int CP, int Cin, float* dw, float* db,
+                       hipStream_t s) {
+  wgrad_reduce(part, G, 1, MT16, 16, CP, 9 * CP, Cin, 16, dw, db, s);
+}
 
 void wgrad_reduce_slots(const float* part, int G, int rows16, int Cout, int Cin, float* dw,
                         float* db, hipStream_t s) {
@@ -1869,6 +1883,10 @@ static bool pool_scatter_on() {
 static bool pool_scatter_shape(int K, int S, int cinp, int cout) {
   return K == 3 && S == 1 && cinp == 4 && cout == 16;
 }
+// the wide-frame stage 0 (wide_pool_wgrad_kernel)
+static bool wide_scatter_shape(int K, int S, int cinp, int cout) {
+  return K == 3 && S == 1 && (cinp == 8 || cinp == 12 || cinp == 16) && cout == 16;
+}
 // workgroups of a pool_wgrad launch (<= tiles): the resident count, 5 per CU
 // at its 96 VGPRs (2-row tiles: 298 -> 228 us against 4-row tiles at 138
 // VGPRs and 2048 slots)
@@ -1887,6 +1905,7 @@ int64_t wgrad_workspace_floats(int K, int Cin, int Cout) {
   const int64_t rows = ((K * K * cinp + 16) / 16) * 16;
   int64_t n = wgrad_slots(K, cinp, Cout) * rows * Cout;
   if (pool_scatter_shape(K, 1, cinp, Cout)) n = std::max<int64_t>(n, int64_t{kPwSlots} * 48 * 16);
+  if (wide_scatter_shape(K, 1, cinp, Cout)) n = std::max<int64_t>(n, kWidePoolWgradSlots * rows * Cout);
   return n;
 }
 
@@ -1906,6 +1925,11 @@ bool conv_launch(const ConvArgs& a, int K, int S, int src, bool flip, hipStream_
   SA_CONV_CASE(4, 16, 3, 1, kSrcU8, false)
   SA_CONV_CASE(4, 16, 3, 1, kSrcF32, false)
   SA_CONV_CASE(4, 32, 8, 4, kSrcF32, false)
+  SA_CONV_CASE(8, 16, 3, 1, kSrcF32, false)   // wide-frame stage 0, dense
+  SA_CONV_CASE(12, 16, 3, 1, kSrcF32, false)
+  SA_CONV_CASE(8, 16, 8, 4, kSrcF32, false)   // wide-frame shallow layer 1
+  SA_CONV_CASE(12, 16, 8, 4, kSrcF32, false)
+  SA_CONV_CASE(16, 16, 8, 4, kSrcF32, false)
   SA_CONV_CASE(16, 16, 3, 1, kSrcF32, false)
   SA_CONV_CASE(16, 32, 3, 1, kSrcF32, false)
   SA_CONV_CASE(32, 32, 3, 1, kSrcF32, false)
@@ -1978,6 +2002,9 @@ bool wgrad_launch(const WgradArgs& a, int K, int S, int src, float* ws, hipStrea
       pool_scatter_shape(K, S, cinp, a.Cout) &&
       run_pool_wgrad(a, ws, src == kSrcU8 ? a.Cin : 0, s))
     return true;
+  if (gather && src == kSrcF32 && pool_scatter_on() && wide_scatter_shape(K, S, cinp, a.Cout)) {
+    if (wide_pool_wgrad_launch(a, ws, s)) return true;
+  }
 #define SA_WG_CASE(CINP, KK, SS, SRC, COUT, NTT, WSM)                                     \
   if (cinp == CINP && K == KK && S == SS && src == SRC && a.Cout == COUT) {               \
     if (gather) return run_wgrad<CINP, KK, SS, SRC, NTT, WSM, true>(a, ws, s);            \
@@ -1986,6 +2013,13 @@ bool wgrad_launch(const WgradArgs& a, int K, int S, int src, float* ws, hipStrea
   SA_WG_CASE(4, 3, 1, kSrcU8, 16, 1, 1)
   SA_WG_CASE(4, 3, 1, kSrcF32, 16, 1, 1)
   SA_WG_CASE(4, 8, 4, kSrcF32, 32, 2, 2)
+  // wide-frame stage 0, dense (SA_F32_POOL_SCATTER=0)
+  SA_WG_CASE(8, 3, 1, kSrcF32, 16, 1, 1)
+  SA_WG_CASE(12, 3, 1, kSrcF32, 16, 1, 1)
+  // wide-frame shallow layer 1 (K = 64 taps x Cp rows, split over the waves)
+  SA_WG_CASE(8, 8, 4, kSrcF32, 32, 2, 4)
+  SA_WG_CASE(12, 8, 4, kSrcF32, 32, 2, 4)
+  SA_WG_CASE(16, 8, 4, kSrcF32, 32, 2, 4)
   SA_WG_CASE(4, 3, 1, kSrcU8, 32, 2, 1)
   SA_WG_CASE(16, 3, 1, kSrcF32, 16, 1, 1)
   SA_WG_CASE(16, 3, 1, kSrcF32, 32, 2, 1)
@@ -2001,6 +2035,8 @@ bool conv_pool_fwd_launch(const ConvArgs& a, int src, int pbh, int pbw, float* p
                           uint8_t* arg, hipStream_t s) {
   if (src == kSrcU8 && a.Cs <= 4 && a.Cout == 16) return run_conv_pool<4, 16, kSrcU8>(a, pbh, pbw, pooled, arg, s);
   if (src == kSrcF32 && a.Cs == 4 && a.Cout == 16) return run_conv_pool<4, 16, kSrcF32>(a, pbh, pbw, pooled, arg, s);
+  if (src == kSrcF32 && a.Cs > 4 && a.Cs <= 16 && a.Cout == 16)
+    return wide_conv_pool_launch(a, pbh, pbw, pooled, arg, s);  // conv_wide.hip
   if (src == kSrcF32 && a.Cs == 16 && a.Cout == 32) return run_conv_pool<16, 32, kSrcF32>(a, pbh, pbw, pooled, arg, s);
   if (src == kSrcF32 && a.Cs == 32 && a.Cout == 32) return run_conv_pool<32, 32, kSrcF32>(a, pbh, pbw, pooled, arg, s);
   return false;
@@ -2103,6 +2139,10 @@ bool shallow_fwd_launch(const uint8_t* frames, const float* w1, const float* b1,
 }
 
 void frames_f32_launch(const uint8_t* x, float* y, int64_t P, int Cs, hipStream_t s) {
+  if (Cs > 4) {
+    frames_f32_wide_launch(x, y, P, Cs, s);  // conv_wide.hip
+    return;
+  }
   static const bool tiled = sa::env_knob("SA_FRAMES_TILE", 1) != 0;  // 0: one pixel per thread
   if (tiled && (reinterpret_cast<uintptr_t>(x) & 3) == 0 && Cs >= 1 && Cs <= 4) {
     const int64_t blocks = std::max<int64_t>(1, std::min<int64_t>((P + 1023) / 1024, 8192));

@@ -181,6 +181,9 @@ def _log_torso_blocks(flags, model):
       why = 'the one-launch torso is fp32 only'
     elif agent.torso_kind == 'deep':
       why = 'bf16 inference already runs one kernel per block'
+    elif agent.frame_shape[2] > 4:
+      why = ('%s frames are wide: the x / 255 image and the ops launches of '
+             'the fp32 wide path run' % frame)
     else:
       why = 'the kernel does not take %s frames' % frame
     log.info('actor inference torso blocks: %s (--torso_blocks=whole does not '
@@ -196,8 +199,11 @@ def _log_torso_blocks(flags, model):
     cuda = model.device.type == 'cuda'
     took = agent.torso_head_form(cuda) or ()
     form = agent.torso_stage_form(cuda)
+    wide = agent.frame_shape[2] > 4
     names = ['stage %d %s' % (s, 'fused (one launch)' if s in took else
-                              'declines (runs as stage)') for s in (0, 1)]
+                              'declines (wide frames: the x / 255 image and '
+                              'the wide conv+pool launch)' if wide and s == 0
+                              else 'declines (runs as stage)') for s in (0, 1)]
     log.info('actor inference torso blocks: %s (--torso_blocks=heads on %s '
              'frames: head of %s; last stage: %s)', used,
              'x'.join(str(d) for d in agent.frame_shape), ', '.join(names),
@@ -266,7 +272,9 @@ def _log_torso_precision(model):
   elif asked == 'bf16' and used == 'fp32':
     log.info('actor inference torso precision: fp32 (bf16 inference asked for: '
              'no bf16 %s torso kernel takes %s frames; the exact-fp32 torso '
-             'and core run)', agent.torso_kind, frame)
+             'and core run%s)', agent.torso_kind, frame,
+             ', the ops launches of the wide path' if agent.frame_shape[2] > 4
+             else '')
   elif used == 'bf16' and agent.torso_kind == 'shallow':
     log.info('actor inference torso precision: bf16 (x / 255 and the three '
              'convs of the shallow torso in one bf16 MFMA launch on %s frames)',

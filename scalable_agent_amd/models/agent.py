@@ -48,7 +48,7 @@ def _bf16_torso_ready(agent):
 
 def _hip_torso_ready(agent):
   """Some HIP torso covers the agent: the fused bf16 kernels, else the
-  exact-fp32 kernels (any torso, C <= 4 frames)."""
+  exact-fp32 kernels (any torso, frames of up to 16 channels)."""
   from ..ops import conv_f32
   return _bf16_torso_ready(agent) or conv_f32.supports(agent)
 
@@ -501,11 +501,13 @@ class Agent(nn.Module):
       from ..ops import conv
       cache['wsh16'] = conv.shallow_bf16_pack(self)
     if (self.compute_dtype == torch.float32 and self.torso_kind == 'deep' and
-        self.frame_shape[2] < 4):
-      # the fp32 torso's stage-0 weights padded to the 4-channel image
+        self.frame_shape[2] % 4 != 0):
+      # the fp32 torso's stage-0 weights padded to the image's channels (4,
+      # or 8 / 12 / 16 for wide frames)
       from ..ops.conv import deep_param_list
       w0 = deep_param_list(self)[0]
-      cache['w0pad'] = torch.zeros(w0.shape[:2] + (4,) + w0.shape[3:],
+      cp = (self.frame_shape[2] + 3) // 4 * 4
+      cache['w0pad'] = torch.zeros(w0.shape[:2] + (cp,) + w0.shape[3:],
                                    dtype=w0.dtype, device=dev)
     if self.compute_dtype == torch.bfloat16:
       bf = torch.bfloat16

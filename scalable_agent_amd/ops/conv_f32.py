@@ -16,7 +16,13 @@ Backward: data gradients are the same kernel over the stride-dilated dY with
 flipped/transposed weights (ReLU masks and skip adds in the epilogue);
 weight+bias gradients are a deterministic two-stage reduction accumulated
 straight into the learner's flat gradient buffer (grad_sink).  Frames may
-carry any C <= 4 channels (RGB, or Atari-style stacked grayscale).
+carry any C <= 4 channels (RGB, or Atari-style stacked grayscale), or be
+wide, 5 <= C <= 16 (stacked RGB frames, RGB plus depth / label planes): the
+x / 255 image then has Cp = C rounded up to a multiple of 4 channels, the
+deep torso's stage 0 runs the wide-frame kernels (wide_conv_pool_kernel,
+wide_pool_wgrad_kernel) and the shallow torso's 8x8/4 layer the direct
+kernels' Cp instances; from the first conv's output on every shape is the
+one the other kernels serve.
 """
 
 import torch
@@ -49,7 +55,16 @@ POOL_GATHER = bool(POOL_GATHER_STAGES)
 # Stage 0 (4-channel frames -> 16): the conv's weight gradient is computed
 # straight from (dP, argmax) in scatter form (pool_wgrad_kernel) instead of
 # maxpool_bwd + the dense wgrad; SA_F32_POOL_SCATTER=0 restores the latter.
+# Wide frames (Cp = 8 / 12 / 16): the same switch selects the wide stage-0
+# pair (fused conv + pool forward, scatter wgrad); 0 runs the dense chain
+# conv_fwd + maxpool_fwd / maxpool_bwd + the dense wgrad.
 POOL_SCATTER = os.environ.get('SA_F32_POOL_SCATTER', '1') != '0'
+# widest frame the fp32 torsos take
+MAX_WIDE_C = 16
+# the fused wide stage 0 stages whole image rows: one band of a Cp = 12 / 16
+# image fits its staging registers up to this width, and the image must sit
+# inside one 4 GB buffer descriptor; beyond either the dense chain runs
+WIDE_FUSED_MAX_W = 176
 # uint8 frames straight into the first conv (x / 255 on the way into LDS)
 # instead of one fp32 x/255 image written first: the deep stage-0 kernels
 # measured slower on bytes (conv+pool 639 vs 529 + 120 us, scatter wgrad
@@ -67,9 +82,10 @@ U8_DIRECT = {
 
 
 def supports(agent):
-  """Shapes the fp32 kernels cover: both torsos, uint8 frames with C <= 4."""
+  """Shapes the fp32 kernels cover: both torsos, uint8 frames with 1 to 16
+  channels (5 and up: the wide path)."""
   c = agent.frame_shape[2]
-  return agent.torso_kind in ('deep', 'shallow') and 1 <= c <= 4
+  return agent.torso_kind in ('deep', 'shallow') and 1 <= c <= MAX_WIDE_C
 
 
 def _conv_geom(H, W, k, s):
@@ -85,7 +101,7 @@ class _ShallowTorsoF32(torch.autograd.Function):
     # layer 1 reads the uint8 frames itself (x / 255 on the way into LDS),
     # or a 4-channel fp32 x / 255 image (one 16-B load per pixel)
     x = frames.contiguous()
-    if not U8_DIRECT['shallow']:
+    if not U8_DIRECT['shallow'] or x.shape[3] > 4:  # wide frames: the Cp image
       x = C.cf32_frames_f32(x)
     acts = [x]
     geoms = []
@@ -248,8 +264,9 @@ def _deep_forward(ctx, frames, params, stage=False, heads=False):
   head0 = (C.cf32_head_fwd(x, params[0], params[1])
            if heads and x.dtype == torch.uint8 else [])
   # stage 0 reads a 4-channel fp32 x / 255 image (one 16-B load per pixel
-  # in the conv+pool and scatter-wgrad stagers), or the uint8 frames
-  if not head0 and not U8_DIRECT['deep']:
+  # in the conv+pool and scatter-wgrad stagers), or the uint8 frames; wide
+  # frames (C > 4) always go through their Cp-channel image
+  if not head0 and (not U8_DIRECT['deep'] or x.shape[3] > 4):
     x = C.cf32_frames_f32(x)
   saved, meta = [], []
   p = 0
@@ -279,7 +296,12 @@ def _deep_forward(ctx, frames, params, stage=False, heads=False):
       # with the pool in the Winograd epilogue (the pre-pool map only in
       # LDS); other shapes: the direct conv+pool or conv + maxpool_fwd
       xa, arg = fused
-    elif s in FUSED_POOL_STAGES:
+    elif s in FUSED_POOL_STAGES or (s == 0 and POOL_SCATTER and
+                                    x.dtype == torch.float32 and
+                                    x.shape[3] > 4 and w.shape[3] == 16 and
+                                    W <= WIDE_FUSED_MAX_W and
+                                    x.numel() < 2 ** 30 - 64):
+      # (wide frames: conv + bias + pool + argmax in wide_conv_pool_kernel)
       xa, arg = C.cf32_conv_pool_fwd(x, w, b, pbh, pbw)
     else:
       conv = C.cf32_conv_fwd(x, w, b, 1, 1, 1, H, W)
@@ -349,7 +371,9 @@ def _deep_backward(C, ctx, saved, params, gv, dy):
     # stage 0 on an RGB frame staged as 4 channels: the kernels write
     # the 3-channel weight gradient directly (dw_cin)
     gw = gv[pb]
-    scatter = (s == 0 and POOL_SCATTER and stage_in.shape[3] <= 4
+    # (the 16-channel image keeps the dense gradient: its scatter kernel
+    # measured 1755 us against 1747 us for maxpool_bwd + the dense wgrad)
+    scatter = (s == 0 and POOL_SCATTER and stage_in.shape[3] <= 12
                and dy.shape[3] == 16)
     if s in POOL_GATHER_STAGES or scatter:
       # the conv kernels gather the pre-pool gradient from (dP, argmax)
@@ -451,7 +475,7 @@ def torso_forward_f32(agent, frames):
   cache = getattr(agent, '_inference_cache', None)
   if (cache is not None and cache.get('w0pad') is not None and
       not torch.is_grad_enabled() and not U8_DIRECT['deep']):
-    # an inference agent's stage-0 weights, zero-padded to the image's 4
+    # an inference agent's stage-0 weights, zero-padded to the image's
     # channels once per weight publish (no concatenation kernel per step)
     params = [cache['w0pad']] + params[1:]
   # actor inference (no autograd, a board's worth of frames) of an agent
