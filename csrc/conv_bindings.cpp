@@ -259,6 +259,50 @@ void conv1_pool_bwd(at::Tensor dP, at::Tensor arg, at::Tensor x, at::Tensor dw,
                                   x.size(2), C, pb_h, pb_w, stream(), ptr_or_null(part));
 }
 
+// ---- stage 0 on 5 to 16 frame channels (kernels/conv_wide_bf16.hip) ----
+std::vector<at::Tensor> conv1w_pool_fwd(at::Tensor x, at::Tensor w, at::Tensor b,
+                                        int64_t pb_h, int64_t pb_w) {
+  TORCH_CHECK(x.is_cuda() && x.is_contiguous() && x.scalar_type() == at::kByte &&
+              x.dim() == 4 && x.size(3) >= 5 && x.size(3) <= 16,
+              "conv1w_pool_fwd: frames must be uint8 NHWC with 5 <= C <= 16");
+  const int64_t C = x.size(3);
+  check_w(w, b, C, 16);
+  TORCH_CHECK(b.is_cuda(), "bias must be on the GPU");
+  TORCH_CHECK(x.numel() < (int64_t{1} << 31), "conv1w_pool_fwd: chunk the frames");
+  const c10::DeviceGuard g(x.device());
+  const int64_t N = x.size(0), H = x.size(1), W = x.size(2);
+  const int64_t Hp = (H + 1) / 2, Wo = (W + 1) / 2;
+  auto pooled = at::empty({N, Hp, Wo, 16}, x.options().dtype(at::kBFloat16));
+  auto arg = at::empty({N, Hp, Wo, 16}, x.options());
+  sa::conv::conv1w_pool_fwd_launch(x.data_ptr<uint8_t>(), w.data_ptr<float>(),
+                                   b.data_ptr<float>(), pooled.data_ptr(),
+                                   arg.data_ptr<uint8_t>(), N, H, W, C, pb_h, pb_w,
+                                   stream());
+  return {pooled, arg};
+}
+
+void conv1w_pool_bwd(at::Tensor dP, at::Tensor arg, at::Tensor x, at::Tensor dw,
+                     at::Tensor db, int64_t pb_h, int64_t pb_w) {
+  TORCH_CHECK(x.is_cuda() && x.scalar_type() == at::kByte && x.dim() == 4 &&
+              x.size(3) >= 5 && x.size(3) <= 16 && x.is_contiguous(),
+              "conv1w_pool_bwd: frames must be uint8 NHWC with 5 <= C <= 16");
+  const int64_t C = x.size(3);
+  check_act(dP, "dP", 16);
+  TORCH_CHECK(arg.sizes() == dP.sizes() && arg.scalar_type() == at::kByte &&
+              arg.is_contiguous(), "argmax");
+  TORCH_CHECK(dP.size(0) == x.size(0) && dP.size(1) == (x.size(1) + 1) / 2 &&
+              dP.size(2) == (x.size(2) + 1) / 2, "pooled shape");
+  check_grad(dw, db, C, 16);
+  TORCH_CHECK(dw.is_cuda() && db.is_cuda(), "gradients must be on the GPU");
+  TORCH_CHECK(x.numel() < (int64_t{1} << 31), "conv1w_pool_bwd: chunk the frames");
+  const c10::DeviceGuard g(x.device());
+  auto part = wgrad_part(dw, C, 16, true);
+  sa::conv::conv1w_pool_bwd_launch(dP.data_ptr(), arg.data_ptr<uint8_t>(),
+                                   x.data_ptr<uint8_t>(), dw.data_ptr<float>(),
+                                   db.data_ptr<float>(), x.size(0), x.size(1),
+                                   x.size(2), C, pb_h, pb_w, stream(), ptr_or_null(part));
+}
+
 // ---- the shallow torso on bf16 MFMA (kernels/conv_shallow_bf16.hip) ----
 constexpr int64_t kSbSteps[3] = {8, 16, 18};    // K = 32 steps per layer
 constexpr int64_t kSbCout[3] = {32, 64, 128};
@@ -339,6 +383,9 @@ void register_conv_ops(pybind11::module& m) {
         pybind11::arg("db"), pybind11::arg("relu_act") = true);
   m.def("pool_conv_bwd", &pool_conv_bwd);
   m.def("conv1_pool_bwd", &conv1_pool_bwd);
+  // conv1_pool_fwd / conv1_pool_bwd for frames of 5 to 16 channels
+  m.def("conv1w_pool_fwd", &conv1w_pool_fwd);
+  m.def("conv1w_pool_bwd", &conv1w_pool_bwd);
   m.def("shallow_bf16_fwd", &shallow_bf16_fwd, pybind11::arg("frames"), pybind11::arg("w1p"),
         pybind11::arg("b1"), pybind11::arg("w2p"), pybind11::arg("b2"), pybind11::arg("w3p"),
         pybind11::arg("b3"));

@@ -42,6 +42,25 @@ void conv1_pool_bwd_launch(const void* dP, const uint8_t* argmax,
                            const uint8_t* x, float* dw, float* db, int N,
                            int H, int W, int C, int pb_h, int pb_w, hipStream_t s,
                            float* part = nullptr);
+// Stage 0 on frames of 5 to 16 uint8 channels (conv_wide_bf16.hip): the
+// outputs, argmax codes and gradients of the two launches above, in the same
+// layouts; the frame's channels are zero-padded to Cp = 8 (C <= 8) or 16 in
+// LDS.  Families "conv1w_pool_fwd" / "conv1w_pool_bwd" in launch_info; tile
+// heights follow px_conv1_fwd / px_conv1_bwd under the kernels' own LDS rules.
+void conv1w_pool_fwd_launch(const uint8_t* x, const float* w, const float* b,
+                            void* pooled, uint8_t* argmax, int N, int H, int W,
+                            int C, int pb_h, int pb_w, hipStream_t s);
+void conv1w_pool_bwd_launch(const void* dP, const uint8_t* argmax,
+                            const uint8_t* x, float* dw, float* db, int N,
+                            int H, int W, int C, int pb_h, int pb_w, hipStream_t s,
+                            float* part = nullptr);
+// Between conv_wide_bf16.hip and conv_torso.hip (grid, launch record, the
+// deterministic mode's slot reduce).
+int conv1w_grid(int ntiles, size_t smem, bool bwd, int* grid_max);
+void conv1w_note(bool bwd, int grid, int grid_max, int ntiles, int rows,
+                 bool specialized);
+void wgrad_reduce_slots(const float* part, int slots, int nel, int ndw, float* dw,
+                        float* db, hipStream_t s);
 // Deterministic mode (conv_tune("deterministic", 1)): the wgrad launches
 // above take a slot workspace of this many floats (0 = mode off) and add the
 // per-workgroup slots in a fixed order instead of with float atomics.
@@ -87,7 +106,7 @@ void stage_bf16_fwd_launch(const void* x, const float* w, const float* b,
 // Read-only record of the last launch of a launcher family (host side; the
 // tests assert from it that the path they mean to test actually ran).
 struct LaunchInfo {
-  const char* family;  // "res_conv_fwd", ..., "conv1_pool_bwd"; "" = none yet
+  const char* family;  // "res_conv_fwd", ..., "conv1w_pool_bwd"; "" = none yet
   int grid;            // workgroups launched
   int grid_max;        // persistent grid before the min with ntiles
   int ntiles;          // tiles the workgroups walked

@@ -46,10 +46,19 @@ FUSED_BLOCK_MAX_FRAMES = 512
 
 def supports(agent):
   """Shapes the fused bf16 kernels cover: the deep ResNet on uint8 frames
-  with 3 (RGB: DMLab, Doom) or 4 (stacked Atari frames, BASELINE config #2)
-  channels - conv1 packs a pixel's channels into one bf16x4 MFMA operand;
-  other inputs take the fp32 kernels, ops/conv_f32.py."""
-  return agent.torso_kind == 'deep' and agent.frame_shape[2] in (3, 4)
+  with 3 to 16 channels.  3 (RGB: DMLab, Doom) and 4 (stacked Atari frames,
+  BASELINE config #2) are packed into one bf16x4 MFMA operand per pixel
+  (conv1_pool_fwd / bwd); 5 to 16 are zero-padded to 8 or 16 values in LDS
+  (conv1w_pool_fwd / bwd, csrc/kernels/conv_wide_bf16.hip).  Only stage 0
+  depends on the count.  Other inputs take the fp32 kernels, ops/conv_f32.py."""
+  return agent.torso_kind == 'deep' and 3 <= agent.frame_shape[2] <= 16
+
+
+def _stage0_ops(C, frames):
+  """(forward, backward) stage-0 ops for the frames' channel count."""
+  if frames.shape[3] <= 4:
+    return C.conv1_pool_fwd, C.conv1_pool_bwd
+  return C.conv1w_pool_fwd, C.conv1w_pool_bwd
 
 
 def _pool_pads(h, w):
@@ -100,7 +109,7 @@ def _deep_forward(ctx, fused_block, frames, params):
     H, W = x.shape[1], x.shape[2]
     pb_h, pb_w = _pool_pads(H, W)
     if s == 0:
-      pooled, arg = C.conv1_pool_fwd(x, w, b, pb_h, pb_w)
+      pooled, arg = _stage0_ops(C, x)[0](x, w, b, pb_h, pb_w)
     else:
       pooled, arg = C.conv_pool_fwd(x, w, b, pb_h, pb_w)
     shapes.append((H, W, pb_h, pb_w))
@@ -176,8 +185,8 @@ def _deep_backward(ctx, grad_out):
       dy = C.res_conv_bwd(dt, xa, dy, w1, gviews[i1], gviews[i1 + 1], True)
     H, W, pb_h, pb_w = ctx.shapes[s]
     if s == 0:
-      C.conv1_pool_bwd(dy, arg, frames, gviews[pb], gviews[pb + 1], pb_h,
-                       pb_w)
+      _stage0_ops(C, frames)[1](dy, arg, frames, gviews[pb], gviews[pb + 1],
+                                pb_h, pb_w)
     else:
       x_in = stages[s - 1][2]
       dy = C.pool_conv_bwd(dy, arg, x_in, params[pb], gviews[pb],
@@ -186,11 +195,11 @@ def _deep_backward(ctx, grad_out):
 
 
 def torso_forward(agent, frames):
-  """uint8 frames [N,H,W,C] (C = 3 or 4) -> relu'd conv features [N, flat]
+  """uint8 frames [N,H,W,C] (3 <= C <= 16) -> relu'd conv features [N, flat]
   (bf16).  Batches above conv_f32.MAX_FRAMES frames run in equal chunks."""
   if not supports(agent):
     raise NotImplementedError(
-        'bf16 HIP torso: deep ResNet on 3/4-channel uint8 frames only (got %r, %r)' %
+        'bf16 HIP torso: deep ResNet on uint8 frames of 3 to 16 channels only (got %r, %r)' %
         (agent.torso_kind, agent.frame_shape))
   from .conv_f32 import _chunked
   fn = (_DeepTorsoInfer if (not torch.is_grad_enabled() and
@@ -301,7 +310,7 @@ def torso_forward_stages(agent, frames):
   no form runs conv_pool_fwd + two res_block_fwd.  No autograd."""
   if not supports(agent):
     raise NotImplementedError(
-        'bf16 HIP torso: deep ResNet on 3/4-channel uint8 frames only (got %r, %r)' %
+        'bf16 HIP torso: deep ResNet on uint8 frames of 3 to 16 channels only (got %r, %r)' %
         (agent.torso_kind, agent.frame_shape))
   if frames.dtype != torch.uint8:
     raise TypeError('HIP torso expects uint8 frames, got %s' % frames.dtype)
@@ -318,7 +327,7 @@ def torso_forward_stages(agent, frames):
       x = C.stage_bf16_fwd(x, w, b, *blocks, pb_h, pb_w, last)
       continue
     if s == 0:
-      x = C.conv1_pool_fwd(x, w, b, pb_h, pb_w)[0]
+      x = _stage0_ops(C, x)[0](x, w, b, pb_h, pb_w)[0]
     else:
       x = C.conv_pool_fwd(x, w, b, pb_h, pb_w)[0]
     if forms[s] == 'tail':
