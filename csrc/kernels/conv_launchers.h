@@ -82,9 +82,23 @@ bool shallow_bf16_fwd_launch(const uint8_t* frames, const void* w1p, const float
 // 1 where shallow_bf16_fwd_launch takes N x [H, W, C] uint8 frames (72x96,
 // 84x84 or 72x128 with C <= 4, 1 <= N <= 512), else 0.
 int shallow_bf16_form(int N, int H, int W, int C);
+// The same torso on frames of 5 <= C <= 16 channels (shallow_bf16w_kernel):
+// the frame is padded to Cp = C rounded up to a multiple of 4 (8, 12 or 16)
+// bf16 per pixel and layer 1 runs in bands of output rows.  w1p: the layout
+// above over Wflat = [64 Cp, 32] (8 Cp / 4 K steps: 2 Cp x 2 x 64 x 8
+// elements); w2p / w3p, the alignment rules and the features as above.
+// Reports family "shallow_bf16w" (grid, ntiles = N, rows = the band count);
+// the same conv_tune key caps its grid.  shallow_bf16w_form: 1 for 72x96,
+// 84x84 or 72x128 frames with 5 <= C <= 16 and 1 <= N <= 512, else 0.
+bool shallow_bf16w_fwd_launch(const uint8_t* frames, const void* w1p, const float* b1,
+                              const void* w2p, const float* b2, const void* w3p,
+                              const float* b3, void* out, int N, int H, int W, int C,
+                              hipStream_t s);
+int shallow_bf16w_form(int N, int H, int W, int C);
 // Between conv_shallow_bf16.hip and conv_torso.hip (grid cap, launch record).
 int shallow_bf16_grid_max();
 void shallow_bf16_note(int grid, int grid_max, int ntiles);
+void shallow_bf16w_note(int grid, int grid_max, int ntiles, int bands);
 
 // One-launch stages of the bf16 deep torso's no-grad forward
 // (stage_fwd_kernel), one workgroup per image with the stage's maps in LDS;
@@ -106,11 +120,12 @@ void stage_bf16_fwd_launch(const void* x, const float* w, const float* b,
 // Read-only record of the last launch of a launcher family (host side; the
 // tests assert from it that the path they mean to test actually ran).
 struct LaunchInfo {
-  const char* family;  // "res_conv_fwd", ..., "conv1w_pool_bwd"; "" = none yet
+  const char* family;  // "res_conv_fwd", ..., "shallow_bf16w"; "" = none yet
   int grid;            // workgroups launched
   int grid_max;        // persistent grid before the min with ntiles
   int ntiles;          // tiles the workgroups walked
-  int rows;            // tile height (pooled rows for the pool forwards)
+  int rows;            // tile height (pooled rows for the pool forwards; the band
+                       // count for "shallow_bf16w")
   bool specialized;    // a compile-time geometry was picked
 };
 // family == nullptr or "": the most recent launch of any family.  An unknown

@@ -249,6 +249,188 @@ __global__ __launch_bounds__(kSbThreads) void shallow_bf16_kernel(ShallowBf16Arg
   }
 }
 
+// ---- frames of 5 to 16 channels: shallow_bf16w_kernel ----
+//
+// The frame at Cp = 8 / 12 / 16 bf16 per pixel (C rounded up to a multiple of
+// 4, pad channels zero) does not fit LDS beside a1 and a2, so layer 1 runs in
+// BANDS of R output rows.  LDS: band [4 R + 4][Wp0][Cp] (padded input rows
+// 4 oy0 .. of the band that starts at output row oy0), then a1 and a2 as
+// above.  One ky row of a pixel's 8x8 window is 8 Cp contiguous bf16 = Cp / 4
+// K steps of 32, so layer 1 has 16 / 24 / 32 steps, every operand read is one
+// aligned 16-byte LDS read and its packed weights are the layout above over
+// Wflat = [64 Cp, 32].  A wave keeps its channel tile's layer-1 fragments
+// (64 / 96 / 128 registers) for all bands of an image.
+//
+// A thread stages at most kSbwPx band pixels: it loads the dwords that cover
+// the pixel's C bytes (image rows are dword multiples, a pixel may start at
+// any byte), aligns them with v_alignbyte_b32, clears the bytes past C and
+// expands each byte to a bf16 integer on the way into LDS - no raw-byte
+// buffer.  The loads of band b + 1 are issued before the MFMAs of band b and
+// stay in registers until the barrier behind those MFMAs; the last band's
+// registers hold the layer-2 fragments instead.  a1's and a2's pad rings are
+// zeroed once per workgroup: the epilogues only ever store interiors.
+// Rounding points, grid walk and grid cap are those above; it reports family
+// "shallow_bf16w" (grid, ntiles = N, rows = the band count) to launch_info.
+constexpr int kSbwMt1 = 3;  // layer-1 pixel tiles per wave and band
+constexpr int kSbwPx = 6;   // band pixels staged per thread
+
+struct ShallowBf16wArgs {
+  ShallowBf16Args g;  // pointers and geometry as above; g.C = the frame's C
+  int R, bands;       // layer-1 output rows per band; ceil(H1 / R)
+};
+
+// bytes b0..b3 of v -> four bf16 integers (exact: 8 significant bits)
+__device__ __forceinline__ uint2 sbw_expand(uint32_t v) {
+  const uint32_t f0 = __float_as_uint(static_cast<float>(v & 0xffu));
+  const uint32_t f1 = __float_as_uint(static_cast<float>((v >> 8) & 0xffu));
+  const uint32_t f2 = __float_as_uint(static_cast<float>((v >> 16) & 0xffu));
+  const uint32_t f3 = __float_as_uint(static_cast<float>(v >> 24));
+  return make_uint2((f0 >> 16) | (f1 & 0xffff0000u), (f2 >> 16) | (f3 & 0xffff0000u));
+}
+
+// This thread's pixels of the band of `nrows` padded rows from padded row r0
+// of one image (img: its first dword): q[u] = the pixel's bytes, channels
+// past C and pixels of the TF-SAME ring zero.
+template <int CPQ>
+__device__ __forceinline__ void sbw_fetch(const ShallowBf16Args& a,
+                                          const uint32_t* __restrict__ img, int tid, int r0,
+                                          int nrows, uint32_t (&q)[kSbwPx][CPQ]) {
+  const int npx = nrows * a.Wp0;
+  const uint32_t tail = 0xffffffffu >> (8 * (4 * CPQ - a.C));  // C in (Cp - 4, Cp]
+#pragma unroll
+  for (int u = 0; u < kSbwPx; ++u) {
+    const int e = tid + u * kSbThreads;
+    const int r = e / a.Wp0, x = e - r * a.Wp0;
+    const int iy = r0 + r - a.pt1, ix = x - a.pl1;
+#pragma unroll
+    for (int k = 0; k < CPQ; ++k) q[u][k] = 0u;
+    if (e < npx && static_cast<unsigned>(iy) < static_cast<unsigned>(a.H) &&
+        static_cast<unsigned>(ix) < static_cast<unsigned>(a.W)) {
+      const uint32_t o = static_cast<uint32_t>((iy * a.W + ix) * a.C);
+      // uniform base + 32-bit byte offset: one address register per pixel
+      const uint32_t* s = reinterpret_cast<const uint32_t*>(
+          reinterpret_cast<const unsigned char*>(img) + (o & ~3u));
+      // the pixel's last byte is in dword CPQ - 1 or CPQ from s; the image
+      // ends on a dword, so nothing past it is read
+      const bool extra = ((o + a.C - 1) >> 2) - (o >> 2) >= static_cast<uint32_t>(CPQ);
+      uint32_t d[CPQ + 1];
+#pragma unroll
+      for (int k = 0; k < CPQ; ++k) d[k] = s[k];
+      d[CPQ] = extra ? s[CPQ] : 0u;
+#pragma unroll
+      for (int k = 0; k < CPQ; ++k) q[u][k] = __builtin_amdgcn_alignbyte(d[k + 1], d[k], o & 3u);
+      q[u][CPQ - 1] &= tail;
+    }
+  }
+}
+
+template <int CPQ>
+__device__ __forceinline__ void sbw_put(const uint32_t (&q)[kSbwPx][CPQ], int tid, int npx,
+                                        bf16_t* band) {
+#pragma unroll
+  for (int u = 0; u < kSbwPx; ++u) {
+    const int e = tid + u * kSbThreads;
+    if (e >= npx) continue;
+    uint2* dst = reinterpret_cast<uint2*>(band + e * (4 * CPQ));
+#pragma unroll
+    for (int k = 0; k < CPQ; ++k) dst[k] = sbw_expand(q[u][k]);
+  }
+}
+
+template <int CPQ>
+__global__ __launch_bounds__(kSbThreads) void shallow_bf16w_kernel(ShallowBf16wArgs wa) {
+  constexpr int CP = 4 * CPQ, KS1 = 8 * CPQ;
+  const ShallowBf16Args& a = wa.g;
+  extern __shared__ __attribute__((aligned(16))) unsigned char sb_smem[];
+  bf16_t* band = reinterpret_cast<bf16_t*>(sb_smem);
+  bf16_t* a1 = band + (4 * wa.R + 4) * a.Wp0 * CP;
+  bf16_t* a2 = a1 + a.Hp1 * a.Wp1 * kSbPitch1;
+  const int n12 = a.Hp1 * a.Wp1 * kSbPitch1 + a.Hp2 * a.Wp2 * kSbPitch2;  // multiple of 8
+  const uint4 z4 = make_uint4(0, 0, 0, 0);
+
+  // both maps' pad rings, once: the first band's barrier orders it
+  for (int e = threadIdx.x; e < n12 / 8; e += kSbThreads) reinterpret_cast<uint4*>(a1)[e] = z4;
+
+  const int ndw = (a.H * a.W * a.C) >> 2;  // whole dwords (shallow_bf16w_form)
+  const int P3 = a.H3 * a.W3;
+  const int Wp0 = a.Wp0, Wp1 = a.Wp1, Wp2 = a.Wp2, R = wa.R;
+  for (int n = blockIdx.x; n < a.N; n += gridDim.x) {
+    int z = 0;  // opaque per image, as in shallow_bf16_kernel
+    asm volatile("" : "+s"(z));
+    const uint4 *w1 = a.w1 + z, *w2 = a.w2 + z, *w3 = a.w3 + z;
+    uint4 wf1[KS1], wf2[16], wf3[18];
+    // and the thread's number: the staged pixels' and the fragments'
+    // addresses and predicates would otherwise be kept across the image loop
+    // (they spilled)
+    int tid = threadIdx.x;
+    asm volatile("" : "+v"(tid));
+    const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const uint32_t* img = reinterpret_cast<const uint32_t*>(a.frames) + static_cast<int64_t>(n) * ndw;
+    // one band of layer 1; rows oy0 .. of a1 (the band buffer's row 0 is the
+    // padded frame's row 4 oy0)
+    auto layer1 = [&](int oy0) {
+      const int pt = a.pt2, pl = a.pl2;
+      sb_layer<KS1, 2, kSbwMt1, 4, CP, true>(
+          wf1, band, Wp0, min(R, a.H1 - oy0), a.W1, a.b1,
+          [=](int ks) { return (ks / CPQ) * Wp0 * CP + (ks % CPQ) * 32; },
+          [=](int, int oy, int ox, int co, uint2 v) {
+            *reinterpret_cast<uint2*>(a1 + ((oy0 + oy + pt) * Wp1 + ox + pl) * kSbPitch1 + co) = v;
+          });
+    };
+    auto band_rows = [&](int oy0) { return 4 * min(R, a.H1 - oy0) + 4; };
+    {
+      // the band buffer is free: the previous image's last band ended with a
+      // barrier
+      uint32_t q[kSbwPx][CPQ];
+      sbw_fetch<CPQ>(a, img, tid, 0, band_rows(0), q);
+      load_frags<KS1, 2>(w1, wave % 2, lane, wf1);
+      sbw_put<CPQ>(q, tid, band_rows(0) * Wp0, band);
+    }
+    __syncthreads();
+    int oy0 = 0;
+    for (; oy0 + R < a.H1; oy0 += R) {
+      uint32_t q[kSbwPx][CPQ];
+      sbw_fetch<CPQ>(a, img, tid, 4 * (oy0 + R), band_rows(oy0 + R), q);  // in flight during the MFMAs
+      layer1(oy0);
+      __syncthreads();  // the band's reads are done
+      sbw_put<CPQ>(q, tid, band_rows(oy0 + R) * Wp0, band);
+      __syncthreads();
+    }
+    // in flight during the last band where the registers allow it: beside
+    // the 128 of Cp = 16 they do not (the kernel spilled)
+    if constexpr (CPQ < 4) load_frags<16, 4>(w2, wave % 4, lane, wf2);
+    layer1(oy0);
+    if constexpr (CPQ == 4) load_frags<16, 4>(w2, wave % 4, lane, wf2);
+    load_frags<18, 8>(w3, wave, lane, wf3);  // in flight during layer 2
+    __syncthreads();
+    {
+      const int pt = a.pt3, pl = a.pl3;
+      sb_layer<16, 4, kSbMt2, 2, kSbPitch1, false>(
+          wf2, a1, Wp1, a.H2, a.W2, a.b2,
+          [=](int ks) { return ((ks >> 2) * Wp1 + (ks & 3)) * kSbPitch1; },
+          [=](int, int oy, int ox, int co, uint2 v) {
+            *reinterpret_cast<uint2*>(a2 + ((oy + pt) * Wp2 + ox + pl) * kSbPitch2 + co) = v;
+          });
+    }
+    __syncthreads();
+    {
+      bf16_t* o = a.out + static_cast<int64_t>(n) * P3 * 128;
+      sb_layer<18, 8, kSbMt3, 2, kSbPitch2, false>(
+          wf3, a2, Wp2, a.H3, a.W3, a.b3,
+          [=](int ks) {
+            const int tap = ks >> 1;
+            return ((tap / 3) * Wp2 + tap % 3) * kSbPitch2 + (ks & 1) * 32;
+          },
+          [=](int p, int, int, int co, uint2 v) {
+            *reinterpret_cast<uint2*>(o + p * 128 + co) = v;
+          });
+    }
+    // the next image's first write to a1 (band 0's epilogue) is behind one
+    // barrier and layer 2's reads ended at the barrier before layer 3; its
+    // first write to a2 (layer 2) is behind at least two
+  }
+}
+
 // TF-SAME geometry of one conv: output size, pad_before, padded input size
 // (0 where the pad would be negative: not a shape of this torso).
 bool sb_geom(int n, int k, int s, int* out, int* before, int* padded) {
@@ -259,9 +441,8 @@ bool sb_geom(int n, int k, int s, int* out, int* before, int* padded) {
   return total >= 0;
 }
 
-// Geometry and LDS bytes on [H, W, C] frames; 0 where it does not fit the
-// kernel's buffers and wave split.
-size_t sb_plan(int H, int W, int C, ShallowBf16Args* a) {
+// The three layers' geometry on [H, W, C] frames.
+bool sb_dims(int H, int W, int C, ShallowBf16Args* a) {
   a->H = H; a->W = W; a->C = C;
   bool ok = sb_geom(H, 8, 4, &a->H1, &a->pt1, &a->Hp0);
   ok = sb_geom(W, 8, 4, &a->W1, &a->pl1, &a->Wp0) && ok;
@@ -269,7 +450,13 @@ size_t sb_plan(int H, int W, int C, ShallowBf16Args* a) {
   ok = sb_geom(a->W1, 4, 2, &a->W2, &a->pl2, &a->Wp1) && ok;
   ok = sb_geom(a->H2, 3, 2, &a->H3, &a->pt3, &a->Hp2) && ok;
   ok = sb_geom(a->W2, 3, 2, &a->W3, &a->pl3, &a->Wp2) && ok;
-  if (!ok) return 0;
+  return ok;
+}
+
+// Geometry and LDS bytes on [H, W, C] frames; 0 where it does not fit the
+// kernel's buffers and wave split.
+size_t sb_plan(int H, int W, int C, ShallowBf16Args* a) {
+  if (!sb_dims(H, W, C, a)) return 0;
   const size_t f0 = static_cast<size_t>(a->Hp0) * a->Wp0 * 4 * 2;
   const size_t f1 = static_cast<size_t>(a->Hp1) * a->Wp1 * kSbPitch1 * 2;
   const size_t f2 = static_cast<size_t>(a->Hp2) * a->Wp2 * kSbPitch2 * 2;
@@ -283,6 +470,37 @@ size_t sb_plan(int H, int W, int C, ShallowBf16Args* a) {
     return 0;
   const size_t bytes = f0 + f1 + f2;
   return bytes <= kSbLdsMax ? bytes : 0;
+}
+
+// shallow_bf16w_kernel on [H, W, C] frames, 5 <= C <= 16: geometry, the band
+// height R and the LDS bytes; 0 where it does not fit.  R is the most rows
+// whose band [4 R + 4][Wp0][Cp] fits beside a1 and a2 in 160 KB (72x128x16:
+// 82512 bytes at 4224 per row, R = 3; 72x96x16: 101648 at 3200, R = 6) within
+// the kernel's kSbwPx staged pixels per thread and kSbwMt1 tiles per wave,
+// then evened out over the band count.
+size_t sbw_plan(int H, int W, int C, ShallowBf16wArgs* wa) {
+  ShallowBf16Args* a = &wa->g;
+  if (C < 5 || C > 16 || !sb_dims(H, W, C, a)) return 0;
+  const int Cp = (C + 3) / 4 * 4;
+  const size_t row = static_cast<size_t>(a->Wp0) * Cp * 2;
+  const size_t f1 = static_cast<size_t>(a->Hp1) * a->Wp1 * kSbPitch1 * 2;
+  const size_t f2 = static_cast<size_t>(a->Hp2) * a->Wp2 * kSbPitch2 * 2;
+  // 16-byte operand reads and regions; whole dwords per image
+  if (a->Wp0 % 2 != 0 || f1 % 16 != 0 || f2 % 16 != 0) return 0;
+  if ((static_cast<size_t>(H) * W * C) % 4 != 0) return 0;
+  const int PW2 = kSbWaves / 4, PW3 = kSbWaves / 8;
+  if ((a->H2 * a->W2 + 15) / 16 > PW2 * kSbMt2 || (a->H3 * a->W3 + 15) / 16 > PW3 * kSbMt3)
+    return 0;
+  if (f1 + f2 + 8 * row > kSbLdsMax) return 0;
+  int rows = static_cast<int>((kSbLdsMax - f1 - f2) / row);
+  rows = std::min(rows, kSbwPx * kSbThreads / a->Wp0);
+  int R = (rows - 4) / 4;
+  R = std::min(R, (kSbWaves / 2) * kSbwMt1 * 16 / a->W1);
+  R = std::min(R, a->H1);
+  if (R < 1) return 0;
+  wa->bands = (a->H1 + R - 1) / R;
+  wa->R = (a->H1 + wa->bands - 1) / wa->bands;
+  return (4 * wa->R + 4) * row + f1 + f2;
 }
 
 }  // namespace
@@ -319,6 +537,47 @@ bool shallow_bf16_fwd_launch(const uint8_t* frames, const void* w1p, const float
     (void)hipGetLastError();  // the launch itself reports an LDS request it cannot meet
   shallow_bf16_note(G, grid_max, N);
   hipLaunchKernelGGL(shallow_bf16_kernel, dim3(G), dim3(kSbThreads), lds, s, a);
+  return true;
+}
+
+int shallow_bf16w_form(int N, int H, int W, int C) {
+  if (N < 1 || N > 512 || C < 5 || C > 16) return 0;
+  if (!((H == 72 && W == 96) || (H == 84 && W == 84) || (H == 72 && W == 128))) return 0;
+  ShallowBf16wArgs wa{};
+  return sbw_plan(H, W, C, &wa) > 0 ? 1 : 0;
+}
+
+bool shallow_bf16w_fwd_launch(const uint8_t* frames, const void* w1p, const float* b1,
+                              const void* w2p, const float* b2, const void* w3p,
+                              const float* b3, void* out, int N, int H, int W, int C,
+                              hipStream_t s) {
+  if (!shallow_bf16w_form(N, H, W, C)) return false;
+  auto mis = [](const void* p, uintptr_t m) { return (reinterpret_cast<uintptr_t>(p) & m) != 0; };
+  if (mis(frames, 3) || mis(w1p, 15) || mis(w2p, 15) || mis(w3p, 15) || mis(out, 7))
+    return false;
+  ShallowBf16wArgs wa{};
+  const size_t lds = sbw_plan(H, W, C, &wa);
+  ShallowBf16Args& a = wa.g;
+  a.frames = frames;
+  a.w1 = static_cast<const uint4*>(w1p);
+  a.w2 = static_cast<const uint4*>(w2p);
+  a.w3 = static_cast<const uint4*>(w3p);
+  a.b1 = b1; a.b2 = b2; a.b3 = b3;
+  a.out = static_cast<bf16_t*>(out);
+  a.N = N;
+  const int grid_max = shallow_bf16_grid_max();
+  const int G = std::min(N, grid_max);
+  auto go = [&](auto kernel) {
+    if (hipFuncSetAttribute(reinterpret_cast<const void*>(kernel),
+                            hipFuncAttributeMaxDynamicSharedMemorySize,
+                            static_cast<int>(lds)) != hipSuccess)
+      (void)hipGetLastError();  // the launch itself reports an LDS request it cannot meet
+    hipLaunchKernelGGL(kernel, dim3(G), dim3(kSbThreads), lds, s, wa);
+  };
+  shallow_bf16w_note(G, grid_max, N, wa.bands);
+  if (C <= 8) go(shallow_bf16w_kernel<2>);
+  else if (C <= 12) go(shallow_bf16w_kernel<3>);
+  else go(shallow_bf16w_kernel<4>);
   return true;
 }
 

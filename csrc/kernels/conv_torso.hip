@@ -1710,11 +1710,11 @@ bool with_geo(int H, int W, int R, F&& f) {
 // Launch records, one per launcher family (launch_info()).
 enum Family { kResConvFwd, kResBlockFwd, kConvPoolFwd, kConv1PoolFwd,
               kResConvBwd, kPoolConvBwd, kConv1PoolBwd, kShallowBf16, kStageBf16,
-              kConv1wPoolFwd, kConv1wPoolBwd, kFamilies };
+              kConv1wPoolFwd, kConv1wPoolBwd, kShallowBf16w, kFamilies };
 constexpr const char* kFamilyName[kFamilies] = {
     "res_conv_fwd", "res_block_fwd", "conv_pool_fwd", "conv1_pool_fwd",
     "res_conv_bwd", "pool_conv_bwd", "conv1_pool_bwd", "shallow_bf16",
-    "stage_bf16", "conv1w_pool_fwd", "conv1w_pool_bwd"};
+    "stage_bf16", "conv1w_pool_fwd", "conv1w_pool_bwd", "shallow_bf16w"};
 LaunchInfo g_launch[kFamilies] = {};
 int g_last_family = -1;
 void note_launch(Family f, int grid, int grid_max, int ntiles, int rows,
@@ -1777,6 +1777,9 @@ int shallow_bf16_grid_max() {
 }
 void shallow_bf16_note(int grid, int grid_max, int ntiles) {
   note_launch(kShallowBf16, grid, grid_max, ntiles, 0, true);
+}
+void shallow_bf16w_note(int grid, int grid_max, int ntiles, int bands) {
+  note_launch(kShallowBf16w, grid, grid_max, ntiles, bands, true);
 }
 
 // conv_wide_bf16.hip: the persistent grid of its stage-0 kernels (cap_fwd /

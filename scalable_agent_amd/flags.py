@@ -110,7 +110,7 @@ def build_parser() -> argparse.ArgumentParser:
                       'for the policy lag either way) for actor throughput.  '
                       'The deep torso runs its fused bf16 kernels; the shallow '
                       'torso runs its actor steps on a one-launch bf16 MFMA '
-                      'kernel for 72x96, 84x84 and 72x128 frames with up to 4 '
+                      'kernel for 72x96, 84x84 and 72x128 frames with 1 to 16 '
                       'channels (other frames keep the exact-fp32 torso and '
                       'core; the start-up log names the precision that '
                       'runs).')

@@ -268,7 +268,9 @@ class Agent(nn.Module):
       # the learner and any call under autograd take the fp32 kernels
       if (self._shallow_bf16_agent() and not torch.is_grad_enabled() and
           frames.shape[0] <= ops.conv.FUSED_BLOCK_MAX_FRAMES and
-          ops.conv.shallow_bf16_form(frames.shape[1:], frames.shape[0])):
+          (ops.conv.shallow_bf16_form(frames.shape[1:], frames.shape[0]) or
+           ops.conv.shallow_bf16_wide_form(frames.shape[1:],
+                                           frames.shape[0]))):
         return ops.torso_forward_shallow_bf16(self, frames)
       # exact fp32 kernels (also for a bf16 agent whose shape the bf16
       # kernels do not cover); unsupported shapes raise, never fall back
@@ -574,12 +576,15 @@ class Agent(nn.Module):
     ops.conv.FUSED_BLOCK_MAX_FRAMES) of this agent's frames runs: 'bf16' /
     'fp32' (HIP kernels) or 'torch'.  Differs from torso_precision() (the
     learner's) for a bf16 shallow agent: its inference torso is the one-launch
-    bf16 kernel where that takes the frame, else the fp32 kernels."""
+    bf16 kernel where that takes the frame (1-4 channels, or 5-16 in its
+    wide form), else the fp32 kernels."""
     if self.backend != 'hip' or not cuda:
       return 'torch'
     if self._shallow_bf16_agent():
       from ..ops import conv
-      return 'bf16' if conv.shallow_bf16_form(self.frame_shape) else 'fp32'
+      return ('bf16' if (conv.shallow_bf16_form(self.frame_shape) or
+                         conv.shallow_bf16_wide_form(self.frame_shape))
+              else 'fp32')
     return torso_precision(self)
 
   def actor_core_fused(self, generator, cuda=True):

@@ -18,7 +18,8 @@ launches above.
 The SHALLOW torso has one bf16 kernel, for actor inference only
 (csrc/kernels/conv_shallow_bf16.hip, torso_forward_shallow_bf16): x / 255 and
 the three convs (8x8/4, 4x4/2, 3x3/2) of a no-grad forward in one launch on
-bf16 MFMA, uint8 frames in, bf16 features out.  It has no backward: the
+bf16 MFMA, uint8 frames of 1 to 16 channels in (1-4: the whole frame in LDS;
+5-16: layer 1 in bands of rows), bf16 features out.  It has no backward: the
 learner, and supports() / TORSO_READY, stay deep-only.
 """
 
@@ -353,12 +354,26 @@ def shallow_bf16_form(frame_shape, frames=1):
           1 <= int(frames) <= FUSED_BLOCK_MAX_FRAMES)
 
 
+def shallow_bf16_wide_form(frame_shape, frames=1):
+  """shallow_bf16_form for the wide kernel (shallow_bf16w_fwd): the same
+  three frame sizes and frame counts with 5 <= C <= 16 channels.  Host
+  arithmetic only (the binding's shallow_bf16w_form says the same)."""
+  if len(frame_shape) != 3:
+    return False
+  h, w, c = (int(d) for d in frame_shape)
+  return ((h, w) in SHALLOW_BF16_FRAMES and 5 <= c <= 16 and
+          1 <= int(frames) <= FUSED_BLOCK_MAX_FRAMES)
+
+
 def shallow_bf16_pack(agent, out=None):
   """The shallow agent's three conv weights in the kernel's bf16 B-operand
-  layout (shallow_bf16_pack); out: three tensors to refresh in place."""
+  layout (shallow_bf16_pack; shallow_bf16w_pack for a frame of more than 4
+  channels); out: three tensors to refresh in place."""
   from .conv_f32 import shallow_param_list
   p = shallow_param_list(agent)
-  packed = ext().shallow_bf16_pack(p[0].detach(), p[2].detach(), p[4].detach())
+  pack = (ext().shallow_bf16w_pack if p[0].shape[2] > 4 else
+          ext().shallow_bf16_pack)
+  packed = pack(p[0].detach(), p[2].detach(), p[4].detach())
   if out is None:
     return tuple(packed)
   for dst, src in zip(out, packed):
@@ -368,7 +383,7 @@ def shallow_bf16_pack(agent, out=None):
 
 def torso_forward_shallow_bf16(agent, frames):
   """uint8 frames [N,H,W,C] -> ReLU'd conv features [N, flat] (bf16) of the
-  shallow torso in one launch; no autograd.  Uses the agent's
+  shallow torso in one launch (the wide kernel for C > 4); no autograd.  Uses the agent's
   _inference_cache['wsh16'] (packed once per weight publish) when present,
   else packs per call.  Raises where the kernel declines."""
   if agent.torso_kind != 'shallow':
@@ -382,8 +397,10 @@ def torso_forward_shallow_bf16(agent, frames):
   if wp is None:
     wp = shallow_bf16_pack(agent)
   p = shallow_param_list(agent)
-  x = ext().shallow_bf16_fwd(frames.contiguous(), wp[0], p[1].detach(),
-                             wp[1], p[3].detach(), wp[2], p[5].detach())
+  fwd = (ext().shallow_bf16w_fwd if frames.shape[-1] > 4 else
+         ext().shallow_bf16_fwd)
+  x = fwd(frames.contiguous(), wp[0], p[1].detach(), wp[1], p[3].detach(),
+          wp[2], p[5].detach())
   return x.reshape(x.shape[0], -1)
 
 
