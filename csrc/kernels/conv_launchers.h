@@ -100,6 +100,47 @@ int shallow_bf16_grid_max();
 void shallow_bf16_note(int grid, int grid_max, int ntiles);
 void shallow_bf16w_note(int grid, int grid_max, int ntiles, int bands);
 
+// The training form of that torso on 1-4 channel frames
+// (conv_shallow_bf16_train.hip): only the three convs run in bf16, features
+// and parameter gradients are fp32.  Maps are dense NHWC: a1 [N,H1,W1,32],
+// a2 [N,H2,W2,64] (post-ReLU bf16), feats [N,H3,W3,128] (post-ReLU fp32,
+// bitwise shallow_bf16_fwd's output once rounded to bf16).  Every launcher
+// returns false (nothing launched) where shallow_bf16_train_form declines or a
+// pointer is not 16-byte aligned (frames: 4), walks the images with one
+// 512-thread workgroup each under the shallow_bf16_grid cap, and reports
+// family "shallow_bf16_train_fwd" / "_bwd_data" / "_wgrad" (grid, ntiles = N).
+// 1 for 72x96, 84x84 or 72x128 frames with 1 <= C <= 4 and 1 <= N <= 8192.
+int shallow_bf16_train_form(int N, int H, int W, int C);
+// fp32 HWIO weights -> the forward's packed operands (shallow_bf16_pack's
+// layout and bits) and the two data gradients' operands
+//   wd[tap][kq][ct][lane][8] = bf16(W[tap][16 ct + (lane & 15)][32 kq + 8 (lane >> 4) + j])
+// (wd2: 16 x 2 x 2, wd3: 9 x 4 x 4 fragments of 64 x 8), in one launch.
+void shallow_bf16_train_pack_launch(const float* w1, const float* w2, const float* w3,
+                                    void* w1p, void* w2p, void* w3p, void* wd2, void* wd3,
+                                    int C, hipStream_t s);
+bool shallow_bf16_train_fwd_launch(const uint8_t* frames, const void* w1p, const float* b1,
+                                   const void* w2p, const float* b2, const void* w3p,
+                                   const float* b3, float* feats, void* a1, void* a2, int N,
+                                   int H, int W, int C, hipStream_t s);
+// dY3m = bf16(dfeats where feats > 0), dA2 = bf16(dgrad3(dY3m) where a2 > 0),
+// dA1 = bf16(dgrad2(dA2) where a1 > 0); fp32 accumulation, one rounding each.
+bool shallow_bf16_bwd_data_launch(const float* dfeats, const float* feats, const void* a2,
+                                  const void* a1, const void* wd3, const void* wd2, void* dy3m,
+                                  void* da2, void* da1, int N, int H, int W, int C,
+                                  hipStream_t s);
+// dw_l += sum over images and pixels of patches(in_l)^T dOut_l (layer 1: the
+// byte sums / 255), db_l += column sums of dOut_l.  One launch per layer
+// writes each workgroup's fp32 partial sums to its own slot of `part`
+// (shallow_bf16_wgrad_part_floats(N) floats), then one launch adds the slots
+// in a fixed order: no float atomics, bitwise reproducible.
+int64_t shallow_bf16_wgrad_part_floats(int N);
+bool shallow_bf16_wgrad_launch(const uint8_t* frames, const void* a1, const void* a2,
+                               const void* dy3m, const void* da2, const void* da1, float* part,
+                               float* dw1, float* db1, float* dw2, float* db2, float* dw3,
+                               float* db3, int N, int H, int W, int C, hipStream_t s);
+// which: 0 fwd, 1 bwd_data, 2 wgrad (conv_torso.hip keeps the launch records)
+void shallow_bf16_train_note(int which, int grid, int grid_max, int ntiles);
+
 // One-launch stages of the bf16 deep torso's no-grad forward
 // (stage_fwd_kernel), one workgroup per image with the stage's maps in LDS;
 // bitwise conv_pool_fwd + two res_block_fwd.  stage_bf16_form: 1 ("stage":

@@ -1710,11 +1710,13 @@ bool with_geo(int H, int W, int R, F&& f) {
 // Launch records, one per launcher family (launch_info()).
 enum Family { kResConvFwd, kResBlockFwd, kConvPoolFwd, kConv1PoolFwd,
               kResConvBwd, kPoolConvBwd, kConv1PoolBwd, kShallowBf16, kStageBf16,
-              kConv1wPoolFwd, kConv1wPoolBwd, kShallowBf16w, kFamilies };
+              kConv1wPoolFwd, kConv1wPoolBwd, kShallowBf16w, kShallowBf16TrainFwd,
+              kShallowBf16BwdData, kShallowBf16Wgrad, kFamilies };
 constexpr const char* kFamilyName[kFamilies] = {
     "res_conv_fwd", "res_block_fwd", "conv_pool_fwd", "conv1_pool_fwd",
     "res_conv_bwd", "pool_conv_bwd", "conv1_pool_bwd", "shallow_bf16",
-    "stage_bf16", "conv1w_pool_fwd", "conv1w_pool_bwd", "shallow_bf16w"};
+    "stage_bf16", "conv1w_pool_fwd", "conv1w_pool_bwd", "shallow_bf16w",
+    "shallow_bf16_train_fwd", "shallow_bf16_bwd_data", "shallow_bf16_wgrad"};
 LaunchInfo g_launch[kFamilies] = {};
 int g_last_family = -1;
 void note_launch(Family f, int grid, int grid_max, int ntiles, int rows,
@@ -1780,6 +1782,10 @@ void shallow_bf16_note(int grid, int grid_max, int ntiles) {
 }
 void shallow_bf16w_note(int grid, int grid_max, int ntiles, int bands) {
   note_launch(kShallowBf16w, grid, grid_max, ntiles, bands, true);
+}
+void shallow_bf16_train_note(int which, int grid, int grid_max, int ntiles) {
+  constexpr Family f[3] = {kShallowBf16TrainFwd, kShallowBf16BwdData, kShallowBf16Wgrad};
+  note_launch(f[which], grid, grid_max, ntiles, 0, true);
 }
 
 // conv_wide_bf16.hip: the persistent grid of its stage-0 kernels (cap_fwd /

@@ -155,7 +155,27 @@ def _make_agent(flags, num_actions, frame_shape, device, seed, dtype=None):
                pipeline_chunks=getattr(flags, 'pipeline_chunks', 1),
                actor_core=getattr(flags, 'actor_core', 'ops'),
                torso_blocks=getattr(flags, 'torso_blocks', 'ops'),
-               torso_stages=getattr(flags, 'torso_stages', 'ops'))
+               torso_stages=getattr(flags, 'torso_stages', 'ops'),
+               torso_dtype=getattr(flags, 'torso_dtype', 'auto'))
+
+
+def _log_learner_torso(flags, agent, device):
+  """The precision of the conv torso the learner's steps run (--torso_dtype)."""
+  from .models.agent import torso_precision
+  used = torso_precision(agent)
+  if getattr(flags, 'torso_dtype', 'auto') != 'bf16':
+    log.info('learner torso: %s', used)
+    return
+  frame = 'x'.join(str(d) for d in agent.frame_shape)
+  if agent.shallow_torso_bf16_train(device.type == 'cuda'):
+    log.info('learner torso: bf16 convs, fp32 features (--torso_dtype=bf16: '
+             'the three convs on bf16 MFMA on %s frames; FC, core and heads '
+             'stay fp32)', frame)
+    return
+  why = ('the learner is not on a GPU' if device.type != 'cuda' else
+         'the bf16 training kernels do not take %s frames' % frame)
+  log.info('learner torso: %s (--torso_dtype=bf16 does not apply: %s)', used,
+           why)
 
 
 def _log_torso_blocks(flags, model):
@@ -653,6 +673,7 @@ def train(flags):
   writer = SummaryWriter(logdir) if rank == 0 else None
 
   agent = _make_agent(flags, num_actions, frame_shape, device, flags.seed)
+  _log_learner_torso(flags, agent, device)
   learner = Learner(agent, flags, device, world_size=world)
   restored = ckpt_lib.restore(flags.logdir, learner)
   if restored is not None:

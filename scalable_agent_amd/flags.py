@@ -166,6 +166,18 @@ def build_parser() -> argparse.ArgumentParser:
                       'same features.  fp32 agents (see --torso_blocks), the '
                       'shallow torso, the learner and the torch backend run as '
                       'with ops; the start-up log names what runs.')
+  p.add_argument('--torso_dtype', default='auto',
+                 choices=['auto', 'fp32', 'bf16'],
+                 help='Precision of the learner\'s conv torso: auto and fp32 = '
+                      'what --dtype runs.  bf16 (only with --torso=shallow, '
+                      '--dtype=fp32 and a HIP backend) = the three convs of the '
+                      'shallow torso, forward and backward, on bf16 MFMA with '
+                      'fp32 accumulation (72x96, 84x84 and 72x128 frames with '
+                      '1-4 channels; other frames keep the fp32 kernels, the '
+                      'start-up log names what runs); the features, the FC '
+                      'GEMM, the core, the heads, V-trace and RMSProp stay '
+                      'fp32.  Actor inference is untouched (see '
+                      '--inference_dtype).')
   p.add_argument('--inference_device', default='auto',
                  help='Device of the actor-inference model: auto = the '
                       'learner device; e.g. cuda:1 or cpu.')
@@ -279,6 +291,17 @@ def check_flags(flags):
     raise SystemExit('--dtype bf16 --torso shallow: the shallow torso has no '
                      'bf16 HIP kernels (its fp32 kernels would run); use '
                      '--dtype fp32, the deep torso, or --backend torch')
+  if getattr(flags, 'torso_dtype', 'auto') == 'bf16':
+    if getattr(flags, 'dtype', 'fp32') == 'bf16':
+      raise SystemExit('--torso_dtype bf16 --dtype bf16: --torso_dtype changes '
+                       'the convs of an fp32 learner only (use --dtype fp32)')
+    if getattr(flags, 'torso', 'shallow') != 'shallow':
+      raise SystemExit('--torso_dtype bf16 --torso deep: the deep torso '
+                       'follows --dtype (use --dtype bf16)')
+    if getattr(flags, 'backend', 'auto') == 'torch':
+      raise SystemExit('--torso_dtype bf16 --backend torch: the bf16 conv '
+                       'torso is a HIP kernel path; the torch backend follows '
+                       '--dtype')
 
 
 def default_flags(**overrides):

@@ -123,8 +123,16 @@ class Agent(nn.Module):
   def __init__(self, num_actions, torso='shallow', frame_shape=(72, 96, 3),
                seed=None, backend='torch', compute_dtype=torch.float32,
                num_value_heads=1, pipeline_chunks=1, actor_core='ops',
-               torso_blocks='ops', torso_stages='ops'):
+               torso_blocks='ops', torso_stages='ops', torso_dtype='auto'):
     super().__init__()
+    # 'bf16': under autograd the three convs of a HIP SHALLOW torso run on
+    # bf16 MFMA with fp32 accumulation (ops/conv.py
+    # torso_forward_shallow_bf16_train) where that takes the frames
+    # (shallow_torso_bf16_train); the features stay fp32 and compute_dtype is
+    # untouched.  'auto' / 'fp32': the exact-fp32 kernels
+    if torso_dtype not in ('auto', 'fp32', 'bf16'):
+      raise ValueError('unknown torso_dtype %r' % (torso_dtype,))
+    self.torso_dtype = torso_dtype
     # 'fused': a no-grad forward of the bf16 HIP deep torso on a board's
     # worth of frames runs each stage whose maps fit a workgroup's LDS as ONE
     # kernel (ops/conv.py torso_forward_stages) where it applies
@@ -272,6 +280,11 @@ class Agent(nn.Module):
            ops.conv.shallow_bf16_wide_form(frames.shape[1:],
                                            frames.shape[0]))):
         return ops.torso_forward_shallow_bf16(self, frames)
+      # the learner of an agent built with torso_dtype='bf16': the three
+      # convs on bf16 MFMA, fp32 features (the fp32 FC GEMM and core follow)
+      if (torch.is_grad_enabled() and self.shallow_torso_bf16_train() and
+          ops.conv.shallow_bf16_train_form(frames.shape[1:])):
+        return ops.conv.torso_forward_shallow_bf16_train(self, frames)
       # exact fp32 kernels (also for a bf16 agent whose shape the bf16
       # kernels do not cover); unsupported shapes raise, never fall back
       return ops.torso_forward_f32(self, frames)
@@ -570,6 +583,17 @@ class Agent(nn.Module):
     """A HIP shallow agent asked to compute in bf16."""
     return (self.backend == 'hip' and self.torso_kind == 'shallow' and
             self.compute_dtype == torch.bfloat16)
+
+  def shallow_torso_bf16_train(self, cuda=True):
+    """True when `torso_dtype='bf16'` is honoured for a forward of CUDA
+    frames under autograd: a HIP shallow agent whose frame shape the bf16
+    training kernels take (72x96, 84x84 or 72x128 with 1-4 channels).
+    Otherwise the exact-fp32 kernels run."""
+    if (self.torso_dtype != 'bf16' or self.backend != 'hip' or not cuda or
+        self.torso_kind != 'shallow'):
+      return False
+    from ..ops import conv
+    return conv.shallow_bf16_train_form(self.frame_shape)
 
   def inference_torso_precision(self, cuda=True):
     """The precision of the torso a no-grad forward of a board's worth (<=

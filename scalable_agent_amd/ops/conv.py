@@ -19,8 +19,15 @@ The SHALLOW torso has one bf16 kernel, for actor inference only
 (csrc/kernels/conv_shallow_bf16.hip, torso_forward_shallow_bf16): x / 255 and
 the three convs (8x8/4, 4x4/2, 3x3/2) of a no-grad forward in one launch on
 bf16 MFMA, uint8 frames of 1 to 16 channels in (1-4: the whole frame in LDS;
-5-16: layer 1 in bands of rows), bf16 features out.  It has no backward: the
-learner, and supports() / TORSO_READY, stay deep-only.
+5-16: layer 1 in bands of rows), bf16 features out.  It has no backward:
+supports() / TORSO_READY stay deep-only.
+
+The shallow LEARNER's bf16 conv path (Agent(torso_dtype='bf16'),
+csrc/kernels/conv_shallow_bf16_train.hip, torso_forward_shallow_bf16_train)
+is a training form of that kernel for 1-4 channel frames: the same forward
+that also saves a1 / a2 and returns fp32 features, a data-gradient kernel and
+weight-gradient kernels.  Only the three convs change precision; the agent's
+compute_dtype stays fp32.
 """
 
 import os
@@ -402,6 +409,63 @@ def torso_forward_shallow_bf16(agent, frames):
   x = fwd(frames.contiguous(), wp[0], p[1].detach(), wp[1], p[3].detach(),
           wp[2], p[5].detach())
   return x.reshape(x.shape[0], -1)
+
+
+def shallow_bf16_train_form(frame_shape):
+  """True where the shallow torso's bf16 TRAINING kernels
+  (csrc/kernels/conv_shallow_bf16_train.hip) take uint8 frames of this
+  [H, W, C] shape: 72x96, 84x84 or 72x128 with 1 to 4 channels (5 to 16
+  channel frames have the inference kernel only).  Host arithmetic only (the
+  binding's shallow_bf16_train_form says the same for up to 8192 frames)."""
+  if len(frame_shape) != 3:
+    return False
+  h, w, c = (int(d) for d in frame_shape)
+  return (h, w) in SHALLOW_BF16_FRAMES and 1 <= c <= 4
+
+
+class _ShallowTorsoBf16(torch.autograd.Function):
+  """x / 255 and the three convs on bf16 MFMA with fp32 accumulation, fp32
+  features out.  Backward: one data-gradient launch (dY3m, dA2, dA1 as bf16
+  maps), one weight-gradient launch per layer into per-workgroup slots and a
+  fixed-order reduce that accumulates into the fp32 gradient sinks.  No host
+  sync, no data-dependent host decision: graph-capturable."""
+
+  @staticmethod
+  def forward(ctx, frames, *params):
+    C = ext()
+    w1, b1, w2, b2, w3, b3 = (p.detach() for p in params)
+    w1p, w2p, w3p, wd2, wd3 = C.shallow_bf16_train_pack(w1, w2, w3)
+    feats, a1, a2 = C.shallow_bf16_train_fwd(frames, w1p, b1, w2p, b2, w3p, b3)
+    ctx.save_for_backward(frames, feats, a1, a2, wd2, wd3, *params)
+    return feats.reshape(feats.shape[0], -1)
+
+  @staticmethod
+  def backward(ctx, grad_out):
+    C = ext()
+    frames, feats, a1, a2, wd2, wd3 = ctx.saved_tensors[:6]
+    params = ctx.saved_tensors[6:]
+    dfeats = grad_out.reshape(feats.shape).to(torch.float32).contiguous()
+    dy3m, da2, da1 = C.shallow_bf16_bwd_data(frames, dfeats, feats, a2, a1,
+                                             wd3, wd2)
+    gviews, direct = grad_sink.sinks(params)
+    C.shallow_bf16_wgrad(frames, a1, a2, dy3m, da2, da1, *gviews)
+    return (None,) + grad_sink.returned(gviews, direct)
+
+
+def torso_forward_shallow_bf16_train(agent, frames):
+  """uint8 frames [N,H,W,C] -> ReLU'd conv features [N, flat] (fp32) of the
+  shallow torso with its three convs on bf16 MFMA, differentiable in the
+  conv parameters (Agent(torso_dtype='bf16') under autograd).  Batches above
+  conv_f32.MAX_FRAMES frames run in equal chunks.  Raises where the kernels
+  decline."""
+  if agent.torso_kind != 'shallow':
+    raise NotImplementedError('shallow bf16 torso on a %r agent' %
+                              (agent.torso_kind,))
+  if frames.dtype != torch.uint8:
+    raise TypeError('HIP torso expects uint8 frames, got %s' % frames.dtype)
+  from .conv_f32 import _chunked, shallow_param_list
+  return _chunked(_ShallowTorsoBf16, frames.contiguous(),
+                  shallow_param_list(agent))
 
 
 def linear_relu(x, w, b):
