@@ -405,13 +405,16 @@ at::Tensor shallow_bf16w_fwd(at::Tensor x, at::Tensor w1p, at::Tensor b1, at::Te
 // ---- its training form (kernels/conv_shallow_bf16_train.hip) ----
 struct SbtDims { int64_t N, H, W, C, H1, W1, H2, W2, H3, W3; };
 
-SbtDims sbt_dims(const at::Tensor& x, const char* name) {
+// form: the launcher's own frame check (shallow_bf16_train_form, its wide
+// sibling, or shallow_bf16_train_back_form for the kernels behind layer 1)
+SbtDims sbt_dims(const at::Tensor& x, const char* name,
+                 int (*form)(int, int, int, int) = sa::conv::shallow_bf16_train_form) {
   TORCH_CHECK(x.is_cuda() && x.is_contiguous() && x.dim() == 4 && x.scalar_type() == at::kByte,
               name, ": frames must be a contiguous uint8 NHWC GPU tensor");
   SbtDims d{x.size(0), x.size(1), x.size(2), x.size(3)};
   TORCH_CHECK(d.N <= INT_MAX && d.H <= INT_MAX && d.W <= INT_MAX && d.C <= INT_MAX &&
-                  sa::conv::shallow_bf16_train_form(static_cast<int>(d.N), static_cast<int>(d.H),
-                                                    static_cast<int>(d.W), static_cast<int>(d.C)),
+                  form(static_cast<int>(d.N), static_cast<int>(d.H), static_cast<int>(d.W),
+                       static_cast<int>(d.C)),
               name, ": no kernel for ", d.N, " frames of ", d.H, "x", d.W, "x", d.C);
   d.H1 = (d.H + 3) / 4; d.W1 = (d.W + 3) / 4;
   d.H2 = (d.H1 + 1) / 2; d.W2 = (d.W1 + 1) / 2;
@@ -436,19 +439,21 @@ void sbt_launched(bool ok, const char* name) {
 // fp32 HWIO w1 [8,8,C<=4,32], w2, w3 -> {w1p, w2p, w3p (shallow_bf16_pack's
 // layout and bits), wd2, wd3 (the data gradients' operands)}: one launch, once
 // per step.
-std::vector<at::Tensor> shallow_bf16_train_pack(at::Tensor w1, at::Tensor w2, at::Tensor w3) {
-  const char* name = "shallow_bf16_train_pack";
+std::vector<at::Tensor> sbt_pack(at::Tensor w1, at::Tensor w2, at::Tensor w3, bool wide) {
+  const char* name = wide ? "shallow_bf16w_train_pack" : "shallow_bf16_train_pack";
   const at::Tensor* ws[3] = {&w1, &w2, &w3};
   for (const at::Tensor* w : ws)
     TORCH_CHECK(w->is_cuda() && w->is_contiguous() && w->scalar_type() == at::kFloat &&
                     w->dim() == 4, name, ": weights must be contiguous fp32 HWIO GPU tensors");
   const int64_t C = w1.size(2);
-  TORCH_CHECK(w1.size(0) == 8 && w1.size(1) == 8 && C >= 1 && C <= 4 && w1.size(3) == 32 &&
+  TORCH_CHECK(w1.size(0) == 8 && w1.size(1) == 8 && C >= (wide ? 5 : 1) &&
+                  C <= (wide ? 16 : 4) && w1.size(3) == 32 &&
                   w2.sizes() == at::IntArrayRef({4, 4, 32, 64}) &&
                   w3.sizes() == at::IntArrayRef({3, 3, 64, 128}),
-              name, ": weights must be [8,8,C<=4,32], [4,4,32,64], [3,3,64,128]");
+              name, ": weights must be [8,8,", (wide ? "5<=C<=16" : "C<=4"),
+              ",32], [4,4,32,64], [3,3,64,128]");
   const c10::DeviceGuard g(w1.device());
-  const int64_t n[5] = {8 * 32 * 32, 16 * 32 * 64, 18 * 32 * 128, 16 * 32 * 64, 9 * 64 * 128};
+  const int64_t n[5] = {2 * sb_cp(C) * 32 * 32, 16 * 32 * 64, 18 * 32 * 128, 16 * 32 * 64, 9 * 64 * 128};
   auto buf = at::empty({n[0] + n[1] + n[2] + n[3] + n[4]}, w1.options().dtype(at::kBFloat16));
   std::vector<at::Tensor> out;
   int64_t o = 0;
@@ -464,13 +469,21 @@ std::vector<at::Tensor> shallow_bf16_train_pack(at::Tensor w1, at::Tensor w2, at
   return out;
 }
 
+std::vector<at::Tensor> shallow_bf16_train_pack(at::Tensor w1, at::Tensor w2, at::Tensor w3) {
+  return sbt_pack(w1, w2, w3, false);
+}
+// w1 [8,8,5<=C<=16,32]: w1p in shallow_bf16w_pack's layout and bits
+std::vector<at::Tensor> shallow_bf16w_train_pack(at::Tensor w1, at::Tensor w2, at::Tensor w3) {
+  return sbt_pack(w1, w2, w3, true);
+}
+
 // -> {feats fp32 [N,H3,W3,128], a1 bf16 [N,H1,W1,32], a2 bf16 [N,H2,W2,64]}
-std::vector<at::Tensor> shallow_bf16_train_fwd(at::Tensor x, at::Tensor w1p, at::Tensor b1,
-                                               at::Tensor w2p, at::Tensor b2, at::Tensor w3p,
-                                               at::Tensor b3) {
-  const char* name = "shallow_bf16_train_fwd";
-  const SbtDims d = sbt_dims(x, name);
-  sbt_check(w1p, at::kBFloat16, {8 * 32 * 32}, name, "w1p");
+std::vector<at::Tensor> sbt_fwd(at::Tensor x, at::Tensor w1p, at::Tensor b1, at::Tensor w2p,
+                                at::Tensor b2, at::Tensor w3p, at::Tensor b3, bool wide) {
+  const char* name = wide ? "shallow_bf16w_train_fwd" : "shallow_bf16_train_fwd";
+  const SbtDims d = sbt_dims(x, name, wide ? sa::conv::shallow_bf16w_train_form
+                                           : sa::conv::shallow_bf16_train_form);
+  sbt_check(w1p, at::kBFloat16, {2 * sb_cp(d.C) * 32 * 32}, name, "w1p");
   sbt_check(w2p, at::kBFloat16, {16 * 32 * 64}, name, "w2p");
   sbt_check(w3p, at::kBFloat16, {18 * 32 * 128}, name, "w3p");
   const at::Tensor* bs[3] = {&b1, &b2, &b3};
@@ -482,7 +495,9 @@ std::vector<at::Tensor> shallow_bf16_train_fwd(at::Tensor x, at::Tensor w1p, at:
   auto feats = at::empty({d.N, d.H3, d.W3, 128}, x.options().dtype(at::kFloat));
   auto a1 = at::empty({d.N, d.H1, d.W1, 32}, x.options().dtype(at::kBFloat16));
   auto a2 = at::empty({d.N, d.H2, d.W2, 64}, x.options().dtype(at::kBFloat16));
-  sbt_launched(sa::conv::shallow_bf16_train_fwd_launch(
+  const auto launch = wide ? sa::conv::shallow_bf16w_train_fwd_launch
+                           : sa::conv::shallow_bf16_train_fwd_launch;
+  sbt_launched(launch(
                    x.data_ptr<uint8_t>(), w1p.data_ptr(), b1.data_ptr<float>(), w2p.data_ptr(),
                    b2.data_ptr<float>(), w3p.data_ptr(), b3.data_ptr<float>(),
                    feats.data_ptr<float>(), a1.data_ptr(), a2.data_ptr(), static_cast<int>(d.N),
@@ -491,13 +506,24 @@ std::vector<at::Tensor> shallow_bf16_train_fwd(at::Tensor x, at::Tensor w1p, at:
   return {feats, a1, a2};
 }
 
-// frames: only their shape is read.  -> {dY3m [N,H3,W3,128], dA2 [N,H2,W2,64],
+std::vector<at::Tensor> shallow_bf16_train_fwd(at::Tensor x, at::Tensor w1p, at::Tensor b1,
+                                               at::Tensor w2p, at::Tensor b2, at::Tensor w3p,
+                                               at::Tensor b3) {
+  return sbt_fwd(x, w1p, b1, w2p, b2, w3p, b3, false);
+}
+std::vector<at::Tensor> shallow_bf16w_train_fwd(at::Tensor x, at::Tensor w1p, at::Tensor b1,
+                                                at::Tensor w2p, at::Tensor b2, at::Tensor w3p,
+                                                at::Tensor b3) {
+  return sbt_fwd(x, w1p, b1, w2p, b2, w3p, b3, true);
+}
+
+// frames: only their shape is read (1 to 16 channels).  -> {dY3m [N,H3,W3,128], dA2 [N,H2,W2,64],
 // dA1 [N,H1,W1,32]}, bf16
 std::vector<at::Tensor> shallow_bf16_bwd_data(at::Tensor x, at::Tensor dfeats, at::Tensor feats,
                                               at::Tensor a2, at::Tensor a1, at::Tensor wd3,
                                               at::Tensor wd2) {
   const char* name = "shallow_bf16_bwd_data";
-  const SbtDims d = sbt_dims(x, name);
+  const SbtDims d = sbt_dims(x, name, sa::conv::shallow_bf16_train_back_form);
   sbt_check(dfeats, at::kFloat, {d.N, d.H3, d.W3, 128}, name, "dfeats");
   sbt_check(feats, at::kFloat, {d.N, d.H3, d.W3, 128}, name, "feats");
   sbt_check(a2, at::kBFloat16, {d.N, d.H2, d.W2, 64}, name, "a2");
@@ -518,11 +544,12 @@ std::vector<at::Tensor> shallow_bf16_bwd_data(at::Tensor x, at::Tensor dfeats, a
 }
 
 // dw_l / db_l (fp32, HWIO / [cout]) are ACCUMULATED into.
-void shallow_bf16_wgrad(at::Tensor x, at::Tensor a1, at::Tensor a2, at::Tensor dy3m,
-                        at::Tensor da2, at::Tensor da1, at::Tensor dw1, at::Tensor db1,
-                        at::Tensor dw2, at::Tensor db2, at::Tensor dw3, at::Tensor db3) {
-  const char* name = "shallow_bf16_wgrad";
-  const SbtDims d = sbt_dims(x, name);
+void sbt_wgrad(at::Tensor x, at::Tensor a1, at::Tensor a2, at::Tensor dy3m, at::Tensor da2,
+               at::Tensor da1, at::Tensor dw1, at::Tensor db1, at::Tensor dw2, at::Tensor db2,
+               at::Tensor dw3, at::Tensor db3, bool wide) {
+  const char* name = wide ? "shallow_bf16w_wgrad" : "shallow_bf16_wgrad";
+  const SbtDims d = sbt_dims(x, name, wide ? sa::conv::shallow_bf16w_train_form
+                                           : sa::conv::shallow_bf16_train_form);
   sbt_check(a1, at::kBFloat16, {d.N, d.H1, d.W1, 32}, name, "a1");
   sbt_check(a2, at::kBFloat16, {d.N, d.H2, d.W2, 64}, name, "a2");
   sbt_check(dy3m, at::kBFloat16, {d.N, d.H3, d.W3, 128}, name, "dY3m");
@@ -537,9 +564,13 @@ void shallow_bf16_wgrad(at::Tensor x, at::Tensor a1, at::Tensor a2, at::Tensor d
                 " elements");
   const c10::DeviceGuard g(x.device());
   // stream-ordered slot workspace: every slot is written before it is read
-  auto part = at::empty({sa::conv::shallow_bf16_wgrad_part_floats(static_cast<int>(d.N))},
-                        dw1.options());
-  sbt_launched(sa::conv::shallow_bf16_wgrad_launch(
+  const int64_t floats =
+      wide ? sa::conv::shallow_bf16w_wgrad_part_floats(static_cast<int>(d.N), static_cast<int>(d.C))
+           : sa::conv::shallow_bf16_wgrad_part_floats(static_cast<int>(d.N));
+  auto part = at::empty({floats}, dw1.options());
+  const auto launch = wide ? sa::conv::shallow_bf16w_wgrad_launch
+                           : sa::conv::shallow_bf16_wgrad_launch;
+  sbt_launched(launch(
                    x.data_ptr<uint8_t>(), a1.data_ptr(), a2.data_ptr(), dy3m.data_ptr(),
                    da2.data_ptr(), da1.data_ptr(), part.data_ptr<float>(),
                    dw1.data_ptr<float>(), db1.data_ptr<float>(), dw2.data_ptr<float>(),
@@ -547,6 +578,19 @@ void shallow_bf16_wgrad(at::Tensor x, at::Tensor a1, at::Tensor a2, at::Tensor d
                    static_cast<int>(d.N), static_cast<int>(d.H), static_cast<int>(d.W),
                    static_cast<int>(d.C), stream()),
                name);
+}
+
+void shallow_bf16_wgrad(at::Tensor x, at::Tensor a1, at::Tensor a2, at::Tensor dy3m,
+                        at::Tensor da2, at::Tensor da1, at::Tensor dw1, at::Tensor db1,
+                        at::Tensor dw2, at::Tensor db2, at::Tensor dw3, at::Tensor db3) {
+  sbt_wgrad(x, a1, a2, dy3m, da2, da1, dw1, db1, dw2, db2, dw3, db3, false);
+}
+// 5 to 16 channel frames: layers 2 / 3 as above, layer 1 band by band
+// (family "shallow_bf16w_wgrad1"), one reduce
+void shallow_bf16w_wgrad(at::Tensor x, at::Tensor a1, at::Tensor a2, at::Tensor dy3m,
+                         at::Tensor da2, at::Tensor da1, at::Tensor dw1, at::Tensor db1,
+                         at::Tensor dw2, at::Tensor db2, at::Tensor dw3, at::Tensor db3) {
+  sbt_wgrad(x, a1, a2, dy3m, da2, da1, dw1, db1, dw2, db2, dw3, db3, true);
 }
 
 }  // namespace
@@ -560,6 +604,14 @@ void register_conv_ops(pybind11::module& m) {
   m.def("shallow_bf16_wgrad", &shallow_bf16_wgrad);
   m.def("shallow_bf16_train_form", [](int N, int H, int W, int C) {
     return sa::conv::shallow_bf16_train_form(N, H, W, C);
+  });
+  // the same for uint8 frames of 5 <= C <= 16 channels (shallow_bf16_bwd_data
+  // serves both)
+  m.def("shallow_bf16w_train_pack", &shallow_bf16w_train_pack);
+  m.def("shallow_bf16w_train_fwd", &shallow_bf16w_train_fwd);
+  m.def("shallow_bf16w_wgrad", &shallow_bf16w_wgrad);
+  m.def("shallow_bf16w_train_form", [](int N, int H, int W, int C) {
+    return sa::conv::shallow_bf16w_train_form(N, H, W, C);
   });
   m.def("conv1_pool_fwd", &conv1_pool_fwd);
   m.def("conv_pool_fwd", &conv_pool_fwd);

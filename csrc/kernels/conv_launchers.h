@@ -138,7 +138,31 @@ bool shallow_bf16_wgrad_launch(const uint8_t* frames, const void* a1, const void
                                const void* dy3m, const void* da2, const void* da1, float* part,
                                float* dw1, float* db1, float* dw2, float* db2, float* dw3,
                                float* db3, int N, int H, int W, int C, hipStream_t s);
-// which: 0 fwd, 1 bwd_data, 2 wgrad (conv_torso.hip keeps the launch records)
+// The same on frames of 5 <= C <= 16 channels.  shallow_bf16w_train_form: 1
+// for the three frame sizes with 5 <= C <= 16 and 1 <= N <= 8192.  The pack
+// launcher above takes such a w1 (w1p: shallow_bf16w_pack's layout and bits,
+// 2 Cp K steps).  The forward is shallow_bf16w_kernel's banded image loop with
+// the saved maps (family "shallow_bf16w_train_fwd"; feats.to(bf16) is bitwise
+// shallow_bf16w_fwd's output).  The data gradient is
+// shallow_bf16_bwd_data_launch: it reads no frame bytes and takes whatever
+// shallow_bf16_train_back_form accepts (the three sizes, 1 <= C <= 16).  The
+// weight-gradient launcher runs layers 2 and 3 as above (family
+// "shallow_bf16_wgrad"), layer 1 band by band (family "shallow_bf16w_wgrad1")
+// and the same fixed-order reduce; part:
+// shallow_bf16w_wgrad_part_floats(N, C) floats.
+int shallow_bf16w_train_form(int N, int H, int W, int C);
+int shallow_bf16_train_back_form(int N, int H, int W, int C);
+bool shallow_bf16w_train_fwd_launch(const uint8_t* frames, const void* w1p, const float* b1,
+                                    const void* w2p, const float* b2, const void* w3p,
+                                    const float* b3, float* feats, void* a1, void* a2, int N,
+                                    int H, int W, int C, hipStream_t s);
+int64_t shallow_bf16w_wgrad_part_floats(int N, int C);
+bool shallow_bf16w_wgrad_launch(const uint8_t* frames, const void* a1, const void* a2,
+                                const void* dy3m, const void* da2, const void* da1, float* part,
+                                float* dw1, float* db1, float* dw2, float* db2, float* dw3,
+                                float* db3, int N, int H, int W, int C, hipStream_t s);
+// which: 0 fwd, 1 bwd_data, 2 wgrad, 3 the wide fwd, 4 the wide layer-1 wgrad
+// (conv_torso.hip keeps the launch records)
 void shallow_bf16_train_note(int which, int grid, int grid_max, int ntiles);
 
 // One-launch stages of the bf16 deep torso's no-grad forward

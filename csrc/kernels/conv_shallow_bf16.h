@@ -6,6 +6,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstdint>
 
 #include "conv_common.h"
@@ -158,6 +159,105 @@ inline size_t sb_plan(int H, int W, int C, ShallowBf16Args* a) {
     return 0;
   const size_t bytes = f0 + f1 + f2;
   return bytes <= kSbLdsMax ? bytes : 0;
+}
+
+// ---- frames of 5 to 16 channels (shallow_bf16w_kernel and the learner's wide
+// kernels; see conv_shallow_bf16.hip for the band layout) ----
+constexpr int kSbwMt1 = 3;  // layer-1 pixel tiles per wave and band
+constexpr int kSbwPx = 6;   // band pixels staged per thread
+
+struct ShallowBf16wArgs {
+  ShallowBf16Args g;  // pointers and geometry as above; g.C = the frame's C
+  int R, bands;       // layer-1 output rows per band; ceil(H1 / R)
+};
+
+// bytes b0..b3 of v -> four bf16 integers (exact: 8 significant bits)
+__device__ __forceinline__ uint2 sbw_expand(uint32_t v) {
+  const uint32_t f0 = __float_as_uint(static_cast<float>(v & 0xffu));
+  const uint32_t f1 = __float_as_uint(static_cast<float>((v >> 8) & 0xffu));
+  const uint32_t f2 = __float_as_uint(static_cast<float>((v >> 16) & 0xffu));
+  const uint32_t f3 = __float_as_uint(static_cast<float>(v >> 24));
+  return make_uint2((f0 >> 16) | (f1 & 0xffff0000u), (f2 >> 16) | (f3 & 0xffff0000u));
+}
+
+// This thread's pixels of the band of `nrows` padded rows from padded row r0
+// of one image (img: its first dword): q[u] = the pixel's bytes, channels
+// past C and pixels of the TF-SAME ring zero.
+template <int CPQ>
+__device__ __forceinline__ void sbw_fetch(const ShallowBf16Args& a,
+                                          const uint32_t* __restrict__ img, int tid, int r0,
+                                          int nrows, uint32_t (&q)[kSbwPx][CPQ]) {
+  const int npx = nrows * a.Wp0;
+  const uint32_t tail = 0xffffffffu >> (8 * (4 * CPQ - a.C));  // C in (Cp - 4, Cp]
+#pragma unroll
+  for (int u = 0; u < kSbwPx; ++u) {
+    const int e = tid + u * kSbThreads;
+    const int r = e / a.Wp0, x = e - r * a.Wp0;
+    const int iy = r0 + r - a.pt1, ix = x - a.pl1;
+#pragma unroll
+    for (int k = 0; k < CPQ; ++k) q[u][k] = 0u;
+    if (e < npx && static_cast<unsigned>(iy) < static_cast<unsigned>(a.H) &&
+        static_cast<unsigned>(ix) < static_cast<unsigned>(a.W)) {
+      const uint32_t o = static_cast<uint32_t>((iy * a.W + ix) * a.C);
+      // uniform base + 32-bit byte offset: one address register per pixel
+      const uint32_t* s = reinterpret_cast<const uint32_t*>(
+          reinterpret_cast<const unsigned char*>(img) + (o & ~3u));
+      // the pixel's last byte is in dword CPQ - 1 or CPQ from s; the image
+      // ends on a dword, so nothing past it is read
+      const bool extra = ((o + a.C - 1) >> 2) - (o >> 2) >= static_cast<uint32_t>(CPQ);
+      uint32_t d[CPQ + 1];
+#pragma unroll
+      for (int k = 0; k < CPQ; ++k) d[k] = s[k];
+      d[CPQ] = extra ? s[CPQ] : 0u;
+#pragma unroll
+      for (int k = 0; k < CPQ; ++k) q[u][k] = __builtin_amdgcn_alignbyte(d[k + 1], d[k], o & 3u);
+      q[u][CPQ - 1] &= tail;
+    }
+  }
+}
+
+template <int CPQ>
+__device__ __forceinline__ void sbw_put(const uint32_t (&q)[kSbwPx][CPQ], int tid, int npx,
+                                        bf16_t* band) {
+#pragma unroll
+  for (int u = 0; u < kSbwPx; ++u) {
+    const int e = tid + u * kSbThreads;
+    if (e >= npx) continue;
+    uint2* dst = reinterpret_cast<uint2*>(band + e * (4 * CPQ));
+#pragma unroll
+    for (int k = 0; k < CPQ; ++k) dst[k] = sbw_expand(q[u][k]);
+  }
+}
+
+// shallow_bf16w_kernel on [H, W, C] frames, 5 <= C <= 16: geometry, the band
+// height R and the LDS bytes; 0 where it does not fit.  R is the most rows
+// whose band [4 R + 4][Wp0][Cp] fits beside a1 and a2 in 160 KB (72x128x16:
+// 82512 bytes at 4224 per row, R = 3; 72x96x16: 101648 at 3200, R = 6) within
+// the kernel's kSbwPx staged pixels per thread and kSbwMt1 tiles per wave,
+// then evened out over the band count.
+size_t sbw_plan(int H, int W, int C, ShallowBf16wArgs* wa) {
+  ShallowBf16Args* a = &wa->g;
+  if (C < 5 || C > 16 || !sb_dims(H, W, C, a)) return 0;
+  const int Cp = (C + 3) / 4 * 4;
+  const size_t row = static_cast<size_t>(a->Wp0) * Cp * 2;
+  const size_t f1 = static_cast<size_t>(a->Hp1) * a->Wp1 * kSbPitch1 * 2;
+  const size_t f2 = static_cast<size_t>(a->Hp2) * a->Wp2 * kSbPitch2 * 2;
+  // 16-byte operand reads and regions; whole dwords per image
+  if (a->Wp0 % 2 != 0 || f1 % 16 != 0 || f2 % 16 != 0) return 0;
+  if ((static_cast<size_t>(H) * W * C) % 4 != 0) return 0;
+  const int PW2 = kSbWaves / 4, PW3 = kSbWaves / 8;
+  if ((a->H2 * a->W2 + 15) / 16 > PW2 * kSbMt2 || (a->H3 * a->W3 + 15) / 16 > PW3 * kSbMt3)
+    return 0;
+  if (f1 + f2 + 8 * row > kSbLdsMax) return 0;
+  int rows = static_cast<int>((kSbLdsMax - f1 - f2) / row);
+  rows = std::min(rows, kSbwPx * kSbThreads / a->Wp0);
+  int R = (rows - 4) / 4;
+  R = std::min(R, (kSbWaves / 2) * kSbwMt1 * 16 / a->W1);
+  R = std::min(R, a->H1);
+  if (R < 1) return 0;
+  wa->bands = (a->H1 + R - 1) / R;
+  wa->R = (a->H1 + wa->bands - 1) / wa->bands;
+  return (4 * wa->R + 4) * row + f1 + f2;
 }
 
 }  // namespace

@@ -1711,12 +1711,14 @@ bool with_geo(int H, int W, int R, F&& f) {
 enum Family { kResConvFwd, kResBlockFwd, kConvPoolFwd, kConv1PoolFwd,
               kResConvBwd, kPoolConvBwd, kConv1PoolBwd, kShallowBf16, kStageBf16,
               kConv1wPoolFwd, kConv1wPoolBwd, kShallowBf16w, kShallowBf16TrainFwd,
-              kShallowBf16BwdData, kShallowBf16Wgrad, kFamilies };
+              kShallowBf16BwdData, kShallowBf16Wgrad, kShallowBf16wTrainFwd,
+              kShallowBf16wWgrad1, kFamilies };
 constexpr const char* kFamilyName[kFamilies] = {
     "res_conv_fwd", "res_block_fwd", "conv_pool_fwd", "conv1_pool_fwd",
     "res_conv_bwd", "pool_conv_bwd", "conv1_pool_bwd", "shallow_bf16",
     "stage_bf16", "conv1w_pool_fwd", "conv1w_pool_bwd", "shallow_bf16w",
-    "shallow_bf16_train_fwd", "shallow_bf16_bwd_data", "shallow_bf16_wgrad"};
+    "shallow_bf16_train_fwd", "shallow_bf16_bwd_data", "shallow_bf16_wgrad",
+    "shallow_bf16w_train_fwd", "shallow_bf16w_wgrad1"};
 LaunchInfo g_launch[kFamilies] = {};
 int g_last_family = -1;
 void note_launch(Family f, int grid, int grid_max, int ntiles, int rows,
@@ -1784,7 +1786,8 @@ void shallow_bf16w_note(int grid, int grid_max, int ntiles, int bands) {
   note_launch(kShallowBf16w, grid, grid_max, ntiles, bands, true);
 }
 void shallow_bf16_train_note(int which, int grid, int grid_max, int ntiles) {
-  constexpr Family f[3] = {kShallowBf16TrainFwd, kShallowBf16BwdData, kShallowBf16Wgrad};
+  constexpr Family f[5] = {kShallowBf16TrainFwd, kShallowBf16BwdData, kShallowBf16Wgrad,
+                           kShallowBf16wTrainFwd, kShallowBf16wWgrad1};
   note_launch(f[which], grid, grid_max, ntiles, 0, true);
 }
 

@@ -172,6 +172,12 @@ def _log_learner_torso(flags, agent, device):
              'the three convs on bf16 MFMA on %s frames; FC, core and heads '
              'stay fp32)', frame)
     return
+  if agent.shallow_torso_bf16_train_wide(device.type == 'cuda'):
+    log.info('learner torso: bf16 convs, fp32 features (--torso_dtype=bf16: '
+             'the three convs on bf16 MFMA on %s frames, the wide kernels '
+             'with layer 1 in bands of rows; FC, core and heads stay fp32)',
+             frame)
+    return
   why = ('the learner is not on a GPU' if device.type != 'cuda' else
          'the bf16 training kernels do not take %s frames' % frame)
   log.info('learner torso: %s (--torso_dtype=bf16 does not apply: %s)', used,

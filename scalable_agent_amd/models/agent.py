@@ -285,6 +285,10 @@ class Agent(nn.Module):
       if (torch.is_grad_enabled() and self.shallow_torso_bf16_train() and
           ops.conv.shallow_bf16_train_form(frames.shape[1:])):
         return ops.conv.torso_forward_shallow_bf16_train(self, frames)
+      # the same on 5-16 channel frames (the wide training kernels)
+      if (torch.is_grad_enabled() and self.shallow_torso_bf16_train_wide() and
+          ops.conv.shallow_bf16_train_wide_form(frames.shape[1:])):
+        return ops.conv.torso_forward_shallow_bf16_train(self, frames)
       # exact fp32 kernels (also for a bf16 agent whose shape the bf16
       # kernels do not cover); unsupported shapes raise, never fall back
       return ops.torso_forward_f32(self, frames)
@@ -586,14 +590,23 @@ class Agent(nn.Module):
 
   def shallow_torso_bf16_train(self, cuda=True):
     """True when `torso_dtype='bf16'` is honoured for a forward of CUDA
-    frames under autograd: a HIP shallow agent whose frame shape the bf16
-    training kernels take (72x96, 84x84 or 72x128 with 1-4 channels).
-    Otherwise the exact-fp32 kernels run."""
+    frames under autograd by the 1-4 channel kernels: a HIP shallow agent
+    whose frame shape they take (72x96, 84x84 or 72x128 with 1-4 channels).
+    Otherwise shallow_torso_bf16_train_wide() or the exact-fp32 kernels."""
     if (self.torso_dtype != 'bf16' or self.backend != 'hip' or not cuda or
         self.torso_kind != 'shallow'):
       return False
     from ..ops import conv
     return conv.shallow_bf16_train_form(self.frame_shape)
+
+  def shallow_torso_bf16_train_wide(self, cuda=True):
+    """shallow_torso_bf16_train() for the wide training kernels: the same
+    conditions on a frame of 72x96, 84x84 or 72x128 with 5-16 channels."""
+    if (self.torso_dtype != 'bf16' or self.backend != 'hip' or not cuda or
+        self.torso_kind != 'shallow'):
+      return False
+    from ..ops import conv
+    return conv.shallow_bf16_train_wide_form(self.frame_shape)
 
   def inference_torso_precision(self, cuda=True):
     """The precision of the torso a no-grad forward of a board's worth (<=

@@ -24,10 +24,12 @@ supports() / TORSO_READY stay deep-only.
 
 The shallow LEARNER's bf16 conv path (Agent(torso_dtype='bf16'),
 csrc/kernels/conv_shallow_bf16_train.hip, torso_forward_shallow_bf16_train)
-is a training form of that kernel for 1-4 channel frames: the same forward
-that also saves a1 / a2 and returns fp32 features, a data-gradient kernel and
-weight-gradient kernels.  Only the three convs change precision; the agent's
-compute_dtype stays fp32.
+is a training form of that kernel: the same forward that also saves a1 / a2
+and returns fp32 features, a data-gradient kernel and weight-gradient kernels.
+1-4 channel frames run _ShallowTorsoBf16; 5-16 channel frames run
+_ShallowTorsoBf16Wide (the banded forward with saved maps, the same data
+gradient, and a layer-1 weight gradient that walks the frame band by band).
+Only the three convs change precision; the agent's compute_dtype stays fp32.
 """
 
 import os
@@ -412,15 +414,26 @@ def torso_forward_shallow_bf16(agent, frames):
 
 
 def shallow_bf16_train_form(frame_shape):
-  """True where the shallow torso's bf16 TRAINING kernels
-  (csrc/kernels/conv_shallow_bf16_train.hip) take uint8 frames of this
+  """True where the 1-4 channel kernels of the shallow torso's bf16 TRAINING
+  form (csrc/kernels/conv_shallow_bf16_train.hip) take uint8 frames of this
   [H, W, C] shape: 72x96, 84x84 or 72x128 with 1 to 4 channels (5 to 16
-  channel frames have the inference kernel only).  Host arithmetic only (the
+  channel frames: shallow_bf16_train_wide_form).  Host arithmetic only (the
   binding's shallow_bf16_train_form says the same for up to 8192 frames)."""
   if len(frame_shape) != 3:
     return False
   h, w, c = (int(d) for d in frame_shape)
   return (h, w) in SHALLOW_BF16_FRAMES and 1 <= c <= 4
+
+
+def shallow_bf16_train_wide_form(frame_shape):
+  """shallow_bf16_train_form for the wide training kernels
+  (shallow_bf16w_train_fwd, shallow_bf16w_wgrad): the same three frame sizes
+  with 5 <= C <= 16 channels.  Host arithmetic only (the binding's
+  shallow_bf16w_train_form says the same for up to 8192 frames)."""
+  if len(frame_shape) != 3:
+    return False
+  h, w, c = (int(d) for d in frame_shape)
+  return (h, w) in SHALLOW_BF16_FRAMES and 5 <= c <= 16
 
 
 class _ShallowTorsoBf16(torch.autograd.Function):
@@ -452,6 +465,34 @@ class _ShallowTorsoBf16(torch.autograd.Function):
     return (None,) + grad_sink.returned(gviews, direct)
 
 
+class _ShallowTorsoBf16Wide(torch.autograd.Function):
+  """_ShallowTorsoBf16 on 5-16 channel frames: the banded forward with saved
+  maps, the same data-gradient launch (it reads no frame bytes), the layer 2 /
+  3 weight-gradient launches, the banded layer-1 one and the same reduce.
+  Graph-capturable like its sibling."""
+
+  @staticmethod
+  def forward(ctx, frames, *params):
+    C = ext()
+    w1, b1, w2, b2, w3, b3 = (p.detach() for p in params)
+    w1p, w2p, w3p, wd2, wd3 = C.shallow_bf16w_train_pack(w1, w2, w3)
+    feats, a1, a2 = C.shallow_bf16w_train_fwd(frames, w1p, b1, w2p, b2, w3p, b3)
+    ctx.save_for_backward(frames, feats, a1, a2, wd2, wd3, *params)
+    return feats.reshape(feats.shape[0], -1)
+
+  @staticmethod
+  def backward(ctx, grad_out):
+    C = ext()
+    frames, feats, a1, a2, wd2, wd3 = ctx.saved_tensors[:6]
+    params = ctx.saved_tensors[6:]
+    dfeats = grad_out.reshape(feats.shape).to(torch.float32).contiguous()
+    dy3m, da2, da1 = C.shallow_bf16_bwd_data(frames, dfeats, feats, a2, a1,
+                                             wd3, wd2)
+    gviews, direct = grad_sink.sinks(params)
+    C.shallow_bf16w_wgrad(frames, a1, a2, dy3m, da2, da1, *gviews)
+    return (None,) + grad_sink.returned(gviews, direct)
+
+
 def torso_forward_shallow_bf16_train(agent, frames):
   """uint8 frames [N,H,W,C] -> ReLU'd conv features [N, flat] (fp32) of the
   shallow torso with its three convs on bf16 MFMA, differentiable in the
@@ -464,8 +505,8 @@ def torso_forward_shallow_bf16_train(agent, frames):
   if frames.dtype != torch.uint8:
     raise TypeError('HIP torso expects uint8 frames, got %s' % frames.dtype)
   from .conv_f32 import _chunked, shallow_param_list
-  return _chunked(_ShallowTorsoBf16, frames.contiguous(),
-                  shallow_param_list(agent))
+  fn = _ShallowTorsoBf16Wide if frames.shape[-1] > 4 else _ShallowTorsoBf16
+  return _chunked(fn, frames.contiguous(), shallow_param_list(agent))
 
 
 def linear_relu(x, w, b):
