@@ -588,10 +588,14 @@ at::Tensor frames_f32(at::Tensor x) {
 // w1 [8,8,C,32], w2 [4,4,32,64], w3 [3,3,64,128] -> [N,Ho3,Wo3,128], bitwise
 // cf32_frames_f32 + three cf32_conv_fwd(relu_out=True).  Raises on a shape
 // cf32_shallow_form declines.
+template <bool WIDE>
 at::Tensor shallow_fwd(at::Tensor x, at::Tensor w1, at::Tensor b1, at::Tensor w2, at::Tensor b2,
                        at::Tensor w3, at::Tensor b3) {
+  const char* name = WIDE ? "cf32_shallow_wide_fwd" : "cf32_shallow_fwd";
+  const auto form = WIDE ? sa::cf32::shallow_wide_form : sa::cf32::shallow_form;
+  const auto launch = WIDE ? sa::cf32::shallow_wide_fwd_launch : sa::cf32::shallow_fwd_launch;
   check_nhwc(x, "frames");
-  TORCH_CHECK(x.scalar_type() == at::kByte, "cf32_shallow_fwd: frames must be uint8 NHWC");
+  TORCH_CHECK(x.scalar_type() == at::kByte, name, ": frames must be uint8 NHWC");
   const int64_t N = x.size(0), H = x.size(1), W = x.size(2), C = x.size(3);
   const int64_t dims[3][4] = {{8, C, 32, 0}, {4, 32, 64, 0}, {3, 64, 128, 0}};
   const at::Tensor* ws[3] = {&w1, &w2, &w3};
@@ -600,25 +604,25 @@ at::Tensor shallow_fwd(at::Tensor x, at::Tensor w1, at::Tensor b1, at::Tensor w2
     check_w(*ws[i]);
     TORCH_CHECK(ws[i]->size(0) == dims[i][0] && ws[i]->size(2) == dims[i][1] &&
                     ws[i]->size(3) == dims[i][2],
-                "cf32_shallow_fwd: layer ", i + 1, " weights must be HWIO [", dims[i][0], ",",
+                name, ": layer ", i + 1, " weights must be HWIO [", dims[i][0], ",",
                 dims[i][0], ",", dims[i][1], ",", dims[i][2], "]");
     TORCH_CHECK(bs[i]->is_cuda() && bs[i]->scalar_type() == at::kFloat &&
                     bs[i]->is_contiguous() && bs[i]->numel() == dims[i][2], "bias");
   }
   TORCH_CHECK(N <= INT_MAX && H <= INT_MAX && W <= INT_MAX &&
-                  sa::cf32::shallow_form(static_cast<int>(N), static_cast<int>(H),
+                  form(static_cast<int>(N), static_cast<int>(H),
                                          static_cast<int>(W), static_cast<int>(C)),
-              "cf32_shallow_fwd: no kernel for ", N, " frames of ", H, "x", W, "x", C);
+              name, ": no kernel for ", N, " frames of ", H, "x", W, "x", C);
   const c10::DeviceGuard g(x.device());
   const int H1 = (H + 3) / 4, W1 = (W + 3) / 4, H2 = (H1 + 1) / 2, W2 = (W1 + 1) / 2;
   auto y = at::empty({N, (H2 + 1) / 2, (W2 + 1) / 2, 128}, x.options().dtype(at::kFloat));
-  TORCH_CHECK(sa::cf32::shallow_fwd_launch(
+  TORCH_CHECK(launch(
                   x.data_ptr<uint8_t>(), w1.data_ptr<float>(), b1.data_ptr<float>(),
                   w2.data_ptr<float>(), b2.data_ptr<float>(), w3.data_ptr<float>(),
                   b3.data_ptr<float>(), y.data_ptr<float>(), static_cast<int>(N),
                   static_cast<int>(H), static_cast<int>(W), static_cast<int>(C), stream()),
-              "cf32_shallow_fwd: frames must be 4-byte aligned");
-  check_launch("cf32_shallow_fwd");
+              name, ": frames must be 4-byte aligned");
+  check_launch(name);
   return y;
 }
 
@@ -674,12 +678,26 @@ void register_conv_f32_ops(pybind11::module& m) {
   // output rows per workgroup of cf32_res_block_fwd for a C-channel map of
   // width W (0: no instance); tests cross every band seam with it
   m.def("cf32_res_block_band", [](int C, int W) { return sa::cf32::wino_res_block_band(C, W); });
-  m.def("cf32_shallow_fwd", &shallow_fwd, arg("frames"), arg("w1"), arg("b1"), arg("w2"),
+  m.def("cf32_shallow_fwd", &shallow_fwd<false>, arg("frames"), arg("w1"), arg("b1"), arg("w2"),
         arg("b2"), arg("w3"), arg("b3"));
   // 1 where cf32_shallow_fwd takes N uint8 frames of [H, W, C], else 0: the
   // launcher's own decision, host arithmetic only
   m.def("cf32_shallow_form",
         [](int N, int H, int W, int C) { return sa::cf32::shallow_form(N, H, W, C); });
+  // the same on wide frames, C 5..16 (shallow_wide_kernel: layer 1 in bands),
+  // bitwise cf32_frames_f32 + three cf32_conv_fwd on the Cp image and the
+  // zero-padded w1; raises on a shape cf32_shallow_wide_form declines
+  m.def("cf32_shallow_wide_fwd", &shallow_fwd<true>, arg("frames"), arg("w1"), arg("b1"),
+        arg("w2"), arg("b2"), arg("w3"), arg("b3"));
+  m.def("cf32_shallow_wide_form",
+        [](int N, int H, int W, int C) { return sa::cf32::shallow_wide_form(N, H, W, C); });
+  // (layer-1 rows per band, LDS bytes) of cf32_shallow_wide_fwd; (0, 0) where
+  // it declines the frame
+  m.def("cf32_shallow_wide_band", [](int H, int W, int C) {
+    size_t bytes = 0;
+    const int R = sa::cf32::shallow_wide_band(H, W, C, &bytes);
+    return pybind11::make_tuple(R, bytes);
+  });
   m.def("cf32_maxpool_fwd", &maxpool_fwd);
   m.def("cf32_maxpool_bwd", &maxpool_bwd);
   m.def("cf32_relu_mask_", &relu_mask_);

@@ -306,6 +306,24 @@ bool shallow_fwd_launch(const uint8_t* frames, const float* w1, const float* b1,
 // and 72x128 frames, C 1..4, 1 <= N <= kResBlockMaxFrames, and the LDS plan
 // fits), else 0.  Host arithmetic only.
 int shallow_form(int N, int H, int W, int C);
+// The same torso on wide frames, C 5..16 (conv_f32.hip shallow_wide_kernel):
+// layer 1 runs in bands of R output rows over byte rows staged in LDS, with
+// conv_fwd_kernel's K order on the Cp = 8 / 12 / 16 channel image, so the
+// output is bitwise frames_f32_launch + three conv_launch calls on that image
+// and the zero-padded w1; w1 is the UNPADDED [8,8,C,32].  False (nothing
+// launched) where shallow_wide_form declines or a pointer is misaligned.
+// Reports family shallow_whole_wide (rows = R, tiles_per_img = bands).
+bool shallow_wide_fwd_launch(const uint8_t* frames, const float* w1, const float* b1,
+                             const float* w2, const float* b2, const float* w3,
+                             const float* b3, float* out, int N, int H, int W, int C,
+                             hipStream_t s);
+// 1 where shallow_wide_fwd_launch takes N x [H, W, C] uint8 frames (72x96,
+// 84x84 and 72x128, C 5..16, 1 <= N <= kResBlockMaxFrames, the ops launches
+// have a layer-1 tile for the frame (at 72x128 only C 9..12), and some R fits
+// LDS), else 0.  Host arithmetic only.
+int shallow_wide_form(int N, int H, int W, int C);
+// Layer-1 rows per band R of that kernel (0: declined) and its LDS bytes
+int shallow_wide_band(int H, int W, int C, size_t* lds_bytes);
 // Wide-frame stage 0 (conv_wide.hip), reached through frames_f32_launch,
 // conv_pool_fwd_launch and wgrad_launch: false where the shape is not covered
 // (nothing launched).  The scatter gradient writes <= kWidePoolWgradSlots

@@ -725,6 +725,225 @@ __global__ __launch_bounds__(kThreads) void shallow_torso_kernel(ShallowArgs a) 
   }
 }
 
+// ------------------------- whole shallow torso, 5-16 channel (wide) frames
+// The same torso on uint8 frames with 5 <= C <= 16 channels, one workgroup
+// per image.  A wide frame (83 KB at 72x96x12) does not fit beside a1 and a2,
+// so layer 1 runs in bands of R output rows: a band's 4 R + 4 frame rows sit
+// in LDS as bytes, in the region a2 takes after the last band,
+//   band [4R+4][W + 4][C] bytes  row r = frame row 4 oy0 - pt1 + r behind four
+//                                zero pixels, + 4 zero pixels after the last
+// so a tap left of the frame reads the row's zero pixels, one right of it
+// the next row's, and rows above / below the frame are stored as zeros: no
+// tap needs a bounds test, and a zero byte is 0.f through the x / 255 table.
+// The next band's rows are loaded into registers (<= kShwPF dwords per
+// thread) before this band's MFMAs and committed after them.
+//
+// Layer 1's K order is conv_fwd_kernel<Cp, 16, 8, 4>'s on the Cp = 8 / 12 /
+// 16 channel image (VPL = Cp / 4): taps (ky, kx) in order, then v < VPL with
+// channel VPL g + v in k slot g on both operands.  Channels >= C are zero on
+// both: the weight fragment holds 0.f (w1 is read unpadded) and the lane's
+// byte address is that of the zero pixel, never the frame's.  Each output
+// element therefore accumulates the sequence of frames_f32 + conv_fwd on the
+// zero-padded image and weights, bitwise; layers 2 and 3 are shallow_layer.
+//
+// Waves: wave & 1 picks the 16-channel output block, wave >> 1 the parity of
+// the band's 16-pixel groups: kShwG per wave, all of them computed (a group
+// past the band's last pixel reads pixel 0 and is not stored: a branch per
+// MFMA cost ten times the MFMAs it saved).  Per tap a lane fetches VPL
+// bytes per group, looks them up, and feeds VPL MFMAs per group; the next
+// tap's byte reads are issued ahead of this tap's MFMAs.
+constexpr int kShwPF = 32;  // band dwords per thread in flight
+constexpr int kShwG = 5;    // 16-pixel groups per wave per band
+
+template <int VPL>
+__global__ __launch_bounds__(kThreads) void shallow_wide_kernel(ShallowArgs a, int R) {
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  constexpr int SPC = VPL == 2 ? 8 : 4;      // taps per weight chunk
+  constexpr int CHF = SPC * 128 * VPL;       // floats per chunk: [tap][g][co 32][VPL]
+  constexpr int UPT = SPC * 128 / kThreads;  // VPL-float units per thread
+  constexpr int NCH = 64 / SPC;
+  constexpr int MAXG = kShwG;
+  static_assert(CHF <= kShChunk && UPT * kThreads == SPC * 128, "chunking");
+  float* lut = smem;
+  float* zero = lut + 256;
+  float* wbuf = zero + kShZero;
+  float* a1 = wbuf + 2 * kShChunk;
+  float* a2 = a1 + a.H1 * a.W1 * fwd_pitch(32);
+  uint32_t* band32 = reinterpret_cast<uint32_t*>(a2);
+  const uint8_t* band = reinterpret_cast<const uint8_t*>(a2);
+  lut[threadIdx.x] = static_cast<float>(static_cast<double>(threadIdx.x) / 255.0);
+  if (threadIdx.x < kShZero) zero[threadIdx.x] = 0.f;
+  const int C = a.C, W = a.W, H = a.H, W1 = a.W1;
+  const int rowd = (W * C) >> 2;          // dwords per frame row (W % 4 == 0)
+  const int pitchd = ((W + 4) * C) >> 2;  // dwords per band row
+  const float rrowd = 1.f / static_cast<float>(rowd), rw1 = 1.f / static_cast<float>(W1);
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int g = lane >> 4, c16 = lane & 15;
+  const int hsel = wave & 1, gsel = wave >> 1;
+  const int co = 16 * hsel + 4 * g;
+  // byte offset of the zero pixel from the band (negative: it lies below)
+  const int zoff = static_cast<int>(reinterpret_cast<const uint8_t*>(zero) - band);
+  bool chok[VPL];
+#pragma unroll
+  for (int v = 0; v < VPL; ++v) chok[v] = VPL * g + v < C;
+  const int nb = (a.H1 + R - 1) / R;
+
+  uint32_t pf[kShwPF];
+  // band b: output rows [oy0, oy0 + ro), band rows [0, nrows) = frame rows
+  // row0 + r, of which [lo, hi) lie inside the frame
+  auto geom = [&](int b, int& oy0, int& ro, int& row0, int& nrows, int& lo, int& hi) {
+    oy0 = b * R;
+    ro = min(R, a.H1 - oy0);
+    row0 = oy0 * 4 - a.pt1;
+    nrows = 4 * ro + 4;
+    lo = max(row0, 0);
+    hi = min(row0 + nrows, H);
+  };
+  auto bload = [&](int n, int b) {
+    int oy0, ro, row0, nrows, lo, hi;
+    geom(b, oy0, ro, row0, nrows, lo, hi);
+    const int nd = (hi - lo) * rowd;
+    const uint32_t* src = reinterpret_cast<const uint32_t*>(
+        a.frames + (static_cast<int64_t>(n) * H + lo) * (4 * rowd));
+#pragma unroll
+    for (int k = 0; k < kShwPF; ++k) {
+      const int d = threadIdx.x + k * kThreads;
+      pf[k] = d < nd ? src[d] : 0u;
+    }
+  };
+  auto bcommit = [&](int b) {
+    int oy0, ro, row0, nrows, lo, hi;
+    geom(b, oy0, ro, row0, nrows, lo, hi);
+    const int nd = (hi - lo) * rowd;
+    uint32_t* dst = band32 + (lo - row0) * pitchd + C;
+#pragma unroll
+    for (int k = 0; k < kShwPF; ++k) {
+      const int d = threadIdx.x + k * kThreads;
+      if (d < nd) {
+        const int r = fdiv(d, rrowd);
+        dst[r * pitchd + d - r * rowd] = pf[k];
+      }
+    }
+    // rows above / below the frame
+    const int ntop = lo - row0, nbot = row0 + nrows - hi;
+    for (int e = threadIdx.x; e < (ntop + nbot) * rowd; e += kThreads) {
+      const int r = fdiv(e, rrowd);
+      const int rr = r < ntop ? r : nrows - nbot + (r - ntop);
+      band32[rr * pitchd + C + e - r * rowd] = 0u;
+    }
+    // the zero pixels (a2 overwrote them during the previous image)
+    if (b == 0)
+      for (int e = threadIdx.x; e < (4 * R + 5) * C; e += kThreads) {
+        const int r = e / C;
+        band32[r * pitchd + e - r * C] = 0u;
+      }
+  };
+
+  float pre[UPT][VPL];
+  auto wload = [&](int c) {
+#pragma unroll
+    for (int k = 0; k < UPT; ++k) {
+      const int u = threadIdx.x + k * kThreads;
+      const int o = u & 31, q = u >> 5;
+      const int tap = c * SPC + (q >> 2), gq = q & 3;
+#pragma unroll
+      for (int v = 0; v < VPL; ++v) {
+        const int ci = VPL * gq + v;
+        pre[k][v] = ci < C ? a.w1[(tap * C + ci) * 32 + o] : 0.f;
+      }
+    }
+  };
+  auto wcommit = [&](float* buf) {
+#pragma unroll
+    for (int k = 0; k < UPT; ++k) {
+      const int u = threadIdx.x + k * kThreads;
+#pragma unroll
+      for (int v = 0; v < VPL; ++v) buf[u * VPL + v] = pre[k][v];
+    }
+  };
+
+  for (int n = blockIdx.x; n < a.N; n += gridDim.x) {
+    bload(n, 0);
+#pragma unroll 1
+    for (int b = 0; b < nb; ++b) {
+      int oy0, ro, row0, nrows, lo, hi;
+      geom(b, oy0, ro, row0, nrows, lo, hi);
+      // the previous band / the previous image's layer 3 ended with a barrier
+      bcommit(b);
+      if (b + 1 < nb) bload(n, b + 1);  // in flight during the MFMAs below
+      const int P = ro * W1;
+      int abase[MAXG][VPL];
+      f4 acc[MAXG];
+#pragma unroll
+      for (int j = 0; j < MAXG; ++j) {
+        const int p = (gsel + 2 * j) * 16 + c16;
+        const int pp = p < P ? p : 0;
+        const int oy = fdiv(pp, rw1), ox = pp - oy * W1;
+        const int base = (oy * 4 * (W + 4) + ox * 4 - a.pl1 + 4) * C + VPL * g;
+#pragma unroll
+        for (int v = 0; v < VPL; ++v) abase[j][v] = chok[v] ? base + v : zoff;
+        acc[j] = f4{0.f, 0.f, 0.f, 0.f};
+      }
+      uint32_t by[MAXG][VPL];
+      auto bget = [&](int tap) {
+        const int toff = ((tap >> 3) * (W + 4) + (tap & 7)) * C;
+        int tv[VPL];
+#pragma unroll
+        for (int v = 0; v < VPL; ++v) tv[v] = chok[v] ? toff : 0;
+#pragma unroll
+        for (int j = 0; j < MAXG; ++j)
+#pragma unroll
+          for (int v = 0; v < VPL; ++v) by[j][v] = band[abase[j][v] + tv[v]];
+      };
+
+      wload(0);
+      wcommit(wbuf);
+      __syncthreads();  // chunk 0, the band (and at first the table) visible
+      bget(0);
+#pragma unroll 1
+      for (int c = 0; c < NCH; ++c) {
+        const float* wcur = wbuf + (c & 1) * CHF;
+        if (c + 1 < NCH) wload(c + 1);  // in flight during the MFMAs below
+#pragma unroll 1
+        for (int sl = 0; sl < SPC; ++sl) {
+          const int t = c * SPC + sl;
+          float av[VPL], xv[MAXG][VPL];
+          lds_get<VPL>(wcur + ((sl * 4 + g) * 32 + 16 * hsel + c16) * VPL, av);
+#pragma unroll
+          for (int j = 0; j < MAXG; ++j)
+#pragma unroll
+            for (int v = 0; v < VPL; ++v) xv[j][v] = lut[by[j][v]];
+          bget(min(t + 1, 63));  // the next tap's bytes, in flight during the MFMAs
+#pragma unroll
+          for (int v = 0; v < VPL; ++v)
+#pragma unroll
+            for (int j = 0; j < MAXG; ++j) acc[j] = mfma4(av[v], xv[j][v], acc[j]);
+        }
+        if (c + 1 < NCH) {
+          wcommit(wbuf + ((c + 1) & 1) * CHF);
+        } else {
+#pragma unroll
+          for (int j = 0; j < MAXG; ++j) {
+            const int p = (gsel + 2 * j) * 16 + c16;
+            if (p >= P) continue;
+            f4 v = acc[j];
+#pragma unroll
+            for (int r = 0; r < 4; ++r) v[r] = fmaxf(v[r] + a.b1[co + r], 0.f);
+            *reinterpret_cast<f4*>(a1 + (oy0 * W1 + p) * fwd_pitch(32) + co) = v;
+          }
+        }
+        __syncthreads();  // every wave is done with chunk c; chunk c + 1 visible
+      }
+    }
+    shallow_layer<4, 2, 32, 64, 2, 1, 1, kShG2, false>(
+        a.w2, 32, a.b2, a1, lut, zero, a.H1, a.W1, 0, a.pt2, a.pl2, a.H2, a.W2, wbuf, a2,
+        fwd_pitch(64));
+    shallow_layer<3, 2, 64, 128, 4, 2, 1, kShG3, false>(
+        a.w3, 64, a.b3, a2, lut, zero, a.H2, a.W2, 0, a.pt3, a.pl3, a.H3, a.W3, a1,
+        a.out + static_cast<int64_t>(n) * a.H3 * a.W3 * 128, 128);
+  }
+}
+
 // ------------------------------------------------------- fused conv + pool
 // Stage head of the deep torso: conv3x3/1 SAME + bias, then the 3x3/2 SAME
 // max-pool, in one persistent kernel.  A tile is R pooled rows of one image:
@@ -2135,6 +2354,87 @@ bool shallow_fwd_launch(const uint8_t* frames, const float* w1, const float* b1,
   allow_lds(shallow_torso_kernel, lds);
   note_launch("shallow_whole", G, 1, N, 0, 1);
   hipLaunchKernelGGL(shallow_torso_kernel, dim3(G), dim3(kThreads), lds, s, a);
+  return true;
+}
+
+namespace {
+// LDS bytes of shallow_wide_kernel on [H, W, C] frames at R layer-1 rows per
+// band (0: the maps do not fit shallow_layer's wave split)
+size_t shallow_wide_bytes(int H, int W, int C, int R, ShallowArgs* a) {
+  shallow_plan(H, W, C, a);  // the geometry; its own answer is for C <= 4
+  const size_t f1 = static_cast<size_t>(a->H1) * a->W1 * fwd_pitch(32);
+  const size_t f2 = static_cast<size_t>(a->H2) * a->W2 * fwd_pitch(64);
+  if (f1 < 2 * static_cast<size_t>(kShChunk3)) return 0;  // layer 3 streams through a1
+  if ((a->H2 * a->W2 + 15) / 16 > kShG2 || (a->H3 * a->W3 + 15) / 16 > kShG3) return 0;
+  const size_t band = ((static_cast<size_t>(4 * R + 4) * (W + 4) + 4) * C + 15) / 16 * 16;
+  return 4 * (256 + kShZero + 2 * kShChunk + f1) + std::max(4 * f2, band);
+}
+
+// Rows per band: every band costs a wave kShwG groups, so the fewest bands
+// that fit LDS, the prefetch registers and 2 kShwG groups per band, then the
+// rows spread evenly over them.  0: no R fits.
+int shallow_wide_rows(int H, int W, int C) {
+  if (W % 4 != 0) return 0;  // whole dwords per frame row
+  ShallowArgs a{};
+  int Rmax = 0;
+  for (int R = 1;; ++R) {
+    const size_t bytes = shallow_wide_bytes(H, W, C, R, &a);
+    if (R > a.H1 || bytes == 0 || bytes > kLdsHard ||
+        (4 * R + 4) * (W * C / 4) > kShwPF * kThreads || (R * a.W1 + 15) / 16 > 2 * kShwG)
+      break;
+    Rmax = R;
+  }
+  if (Rmax == 0) return 0;
+  const int nb = (a.H1 + Rmax - 1) / Rmax;
+  return (a.H1 + nb - 1) / nb;
+}
+}  // namespace
+
+int shallow_wide_form(int N, int H, int W, int C) {
+  if (N < 1 || N > kResBlockMaxFrames || C < 5 || C > 16) return 0;
+  if (!((H == 72 && W == 96) || (H == 84 && W == 84) || (H == 72 && W == 128))) return 0;
+  // the features are defined as those of the ops launches: decline where
+  // conv_fwd_kernel<Cp, 16, 8, 4> has no tile for the frame (run_conv: one
+  // output row's 8 image rows exceed its staging registers, 72x128 at Cp = 8,
+  // or with its weight slice its LDS, 72x128 at Cp = 16)
+  const int cp = (C + 3) / 4 * 4, Wl = W / 4 * 4 + 4;
+  if (8 * Wl * (cp / 4) > fwd_maxc(cp, 8) * kThreads ||
+      static_cast<size_t>(4) * (64 * 16 * cp + 8 * Wl * fwd_pitch(cp)) > kLdsHard)
+    return 0;
+  return shallow_wide_rows(H, W, C) > 0 ? 1 : 0;
+}
+
+int shallow_wide_band(int H, int W, int C, size_t* lds_bytes) {
+  ShallowArgs a{};
+  const int R = shallow_wide_form(1, H, W, C) ? shallow_wide_rows(H, W, C) : 0;
+  if (lds_bytes != nullptr) *lds_bytes = R > 0 ? shallow_wide_bytes(H, W, C, R, &a) : 0;
+  return R;
+}
+
+bool shallow_wide_fwd_launch(const uint8_t* frames, const float* w1, const float* b1,
+                             const float* w2, const float* b2, const float* w3,
+                             const float* b3, float* out, int N, int H, int W, int C,
+                             hipStream_t s) {
+  if (!shallow_wide_form(N, H, W, C)) return false;
+  if ((reinterpret_cast<uintptr_t>(frames) & 3) != 0 || (reinterpret_cast<uintptr_t>(out) & 15) != 0)
+    return false;
+  ShallowArgs a{};
+  const int R = shallow_wide_rows(H, W, C);
+  const size_t lds = shallow_wide_bytes(H, W, C, R, &a);
+  a.frames = frames;
+  a.w1 = w1; a.b1 = b1; a.w2 = w2; a.b2 = b2; a.w3 = w3; a.b3 = b3;
+  a.out = out;
+  a.N = N;
+  const int G = capped(std::min(N, conv_cus()));
+  const int vpl = (C + 3) / 4;
+  note_launch("shallow_whole_wide", G, 1, N, R, (a.H1 + R - 1) / R);
+  auto go = [&](auto kern) {
+    allow_lds(kern, lds);
+    hipLaunchKernelGGL(kern, dim3(G), dim3(kThreads), lds, s, a, R);
+  };
+  if (vpl == 2) go(shallow_wide_kernel<2>);
+  else if (vpl == 3) go(shallow_wide_kernel<3>);
+  else go(shallow_wide_kernel<4>);
   return true;
 }
 

@@ -193,6 +193,11 @@ def _log_torso_blocks(flags, model):
     hip = (getattr(agent, 'backend', 'torch') == 'hip' and
            model.device.type == 'cuda')
     frame = 'x'.join(str(d) for d in agent.frame_shape)
+    if used == 'whole' and agent.torso_whole_form() == 'shallow_wide':
+      log.info('actor inference torso blocks: whole (shallow_wide: x / 255 and '
+               'the three convs of the shallow torso in one launch on %s '
+               'frames, layer 1 in bands over the uint8 rows)', frame)
+      return
     if used == 'whole':
       log.info('actor inference torso blocks: whole (x / 255 and the three '
                'convs of the shallow torso in one launch on %s frames)', frame)
@@ -208,8 +213,9 @@ def _log_torso_blocks(flags, model):
     elif agent.torso_kind == 'deep':
       why = 'bf16 inference already runs one kernel per block'
     elif agent.frame_shape[2] > 4:
-      why = ('%s frames are wide: the x / 255 image and the ops launches of '
-             'the fp32 wide path run' % frame)
+      why = ('the wide one-launch kernel does not take %s frames: the '
+             'x / 255 image and the ops launches of the fp32 wide path run' %
+             frame)
     else:
       why = 'the kernel does not take %s frames' % frame
     log.info('actor inference torso blocks: %s (--torso_blocks=whole does not '

@@ -147,7 +147,9 @@ def build_parser() -> argparse.ArgumentParser:
                       'stage).  Shallow torso: whole = x / 255 and the three '
                       'convs in ONE kernel, one workgroup per frame, every '
                       'intermediate in LDS (72x96, 84x84 and 72x128 frames '
-                      'with 1-4 channels; other shapes run as ops); fused, '
+                      'with 1-4 channels, or with 5-16 channels, where layer '
+                      '1 runs in bands over the uint8 rows; other shapes run '
+                      'as ops); fused, '
                       'stage and heads have nothing to fuse there and run as '
                       'ops.  whole on a deep torso means heads.  All forms '
                       'give bitwise the same features.  bf16 inference fuses '

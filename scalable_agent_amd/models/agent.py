@@ -688,8 +688,9 @@ class Agent(nn.Module):
     """What `torso_blocks='whole'` runs for a no-grad forward of CUDA frames
     of this agent's shape: 'shallow' (x / 255 and the three convs of the
     shallow torso in one launch: fp32 HIP agent, a frame the kernel takes),
-    or None: not asked for, a deep torso (which runs as 'heads'), or the
-    torso runs as 'ops' there."""
+    'shallow_wide' (the same on a 5-16 channel frame: the banded kernel), or
+    None: not asked for, a deep torso (which runs as 'heads'), or the torso
+    runs as 'ops' there."""
     if (self.torso_blocks != 'whole' or self.backend != 'hip' or not cuda or
         self.torso_kind != 'shallow' or
         self.compute_dtype != torch.float32):
@@ -697,7 +698,8 @@ class Agent(nn.Module):
     from ..ops import conv_f32
     if not conv_f32.supports(self):
       return None
-    return conv_f32.whole_form(self.frame_shape)
+    return (conv_f32.whole_form(self.frame_shape) or
+            conv_f32.whole_wide_form(self.frame_shape))
 
   def _fused_step(self, actions, env_outputs, core_state, generator, epilogue):
     """The T = 1 actor step with the fused core: torso, the torso-FC GEMM

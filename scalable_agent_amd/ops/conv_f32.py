@@ -23,6 +23,12 @@ deep torso's stage 0 runs the wide-frame kernels (wide_conv_pool_kernel,
 wide_pool_wgrad_kernel) and the shallow torso's 8x8/4 layer the direct
 kernels' Cp instances; from the first conv's output on every shape is the
 one the other kernels serve.
+
+Actor inference with torso_blocks='whole' runs the shallow torso as one
+launch: shallow_torso_kernel on 1-4 channel frames (whole_form) and, on wide
+frames, shallow_wide_kernel (whole_wide_form), which stages the uint8 rows of
+a band of layer-1 output rows in LDS, reads w1 unpadded and keeps the K order
+of the Cp instance, so both are bitwise the launches above.
 """
 
 import torch
@@ -245,6 +251,16 @@ def whole_form(frame_shape, frames=1):
   return 'shallow' if ext().cf32_shallow_form(frames, h, w, c) else None
 
 
+def whole_wide_form(frame_shape, frames=1):
+  """What torso_blocks='whole' runs for the shallow torso on `frames` wide
+  frames (5 to 16 channels) of this shape: 'shallow_wide'
+  (cf32_shallow_wide_fwd: x / 255 and the three convs in one launch, layer 1
+  in bands over the uint8 rows) or None (the launches of 'ops').  The
+  launcher's own decision (cf32_shallow_wide_form), host arithmetic only."""
+  h, w, c = frame_shape[0], frame_shape[1], frame_shape[2]
+  return 'shallow_wide' if ext().cf32_shallow_wide_form(frames, h, w, c) else None
+
+
 def _deep_forward(ctx, frames, params, stage=False, heads=False):
   """Forward of the deep torso.  ctx None (_DeepTorsoF32Infer): residual
   blocks run cf32_res_block_fwd (both convs in one launch, t only in LDS,
@@ -465,10 +481,14 @@ def torso_forward_f32(agent, frames):
     # the launches below; the learner and any call under autograd take those
     if (blocks == 'whole' and not torch.is_grad_enabled() and
         agent.compute_dtype == torch.float32 and
-        frames.shape[0] <= FUSED_BLOCK_MAX_FRAMES and
-        whole_form(frames.shape[1:], frames.shape[0])):
-      x = ext().cf32_shallow_fwd(frames, *params)
-      return x.reshape(x.shape[0], -1)
+        frames.shape[0] <= FUSED_BLOCK_MAX_FRAMES):
+      if whole_form(frames.shape[1:], frames.shape[0]):
+        x = ext().cf32_shallow_fwd(frames, *params)
+        return x.reshape(x.shape[0], -1)
+      # wide frames: the banded kernel (no Cp image, no w1 pad launch)
+      if whole_wide_form(frames.shape[1:], frames.shape[0]):
+        x = ext().cf32_shallow_wide_fwd(frames, *params)
+        return x.reshape(x.shape[0], -1)
     return _chunked(_ShallowTorsoF32, frames, params)
   from .conv import deep_param_list
   params = deep_param_list(agent)
